@@ -1,11 +1,20 @@
 #!/usr/bin/env python3
 """bench.py — throughput of the scalar-mul hot path on MI355X, one JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--only NAME] [--no-check] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--only NAME] [--dump-outputs DIR] [--full [--no-check] [--no-cpu-baseline]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in HBM when the
-timed region starts.  The top-level record is BASELINE.json's configs[1]; the other GPU configs are timed in the same run,
+timed region starts.  A plain run times the headline workload (or `--only NAME`) and nothing else: set-up, W warm-up steps,
+K timed steps, the outputs of the last timed step (`--dump-outputs DIR`), one JSON line.  Everything below — the check against
+the oracle, the roofline, the CPU baseline, the other GPU configs and the extras — belongs to `--full`.
+
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy in float32 (byte and flag values, exact):
+batches `points` (n x 2L affine x || y, big-endian bytes) + `infinity`, ECDSA `valid`, recovery `keys` + `valid`, MSMs the one
+`points` row + `infinity`.  Batches of more than 2^16 rows are cut to the same seeded sample of rows (`rows`: their indices).
+Inputs are seeded, so two builds run with the same arguments can be compared output for output.  N > 1: rank 0's outputs.
+
+With --full, the top-level record is BASELINE.json's configs[1]; the other GPU configs are timed in the same run,
 with the same K / W and the same fences.  Their headline numbers are ALSO top-level keys (`var_p256_value`,
 `msm_k256_value`, `var_p384_value` + `_ms_per_step`, `_frac`, `_check`), their compact records are under "configs", and the
 prose that used to be repeated per record is once under "notes": the line stays below 8 KB.
@@ -139,6 +148,19 @@ DEFAULT_SUBS = ["var_p256", "msm_k256", "msm_k256_2p21", "var_p384", "ecdsa_p256
 NOMINAL_PEAK = 256 * 4 * 16 * 2.4e9   # IMAD32/s at the 2.4 GHz peak engine clock (the probe, all CUs multiplying, runs at ~2.1)
 HBM_PEAK_GBPS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md (spec; ~6.3 TB/s achievable)
 ROOFLINE_CONSTS = os.path.join(ROOT, "profiles", "roofline_consts.json")
+DUMP_ROWS, DUMP_SEED = 1 << 16, 0xEC0D0E    # --dump-outputs: at most 2^16 rows (p384 points: 25 MB as float32), one seeded sample
+
+
+def dump_outputs(torch, out_dir, rows, arrays):
+    """--dump-outputs: `arrays` ({name: device tensor with `rows` rows}) as out_dir/<name>.npy in float32, every tensor cut to
+    the same seeded sample of DUMP_ROWS rows when there are more (their indices: rows.npy)."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = np.arange(rows) if rows <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, DUMP_ROWS, replace=False))
+    if rows > DUMP_ROWS:
+        np.save(os.path.join(out_dir, "rows.npy"), idx.astype(np.float64))
+    for name, t in arrays.items():
+        d_idx = torch.from_numpy(idx).to(t.device)
+        np.save(os.path.join(out_dir, name + ".npy"), t[:rows][d_idx].cpu().numpy().astype(np.float32))
 
 
 def roofline_consts(kernel):
@@ -451,8 +473,9 @@ class Bench:
             inp["pts"] = d_Q
         return inp
 
-    def run(self, name, cpu_leg):
-        """Times workload `name`: W warm-up steps, then exactly K steps between fences; returns its record (rank 0) or None."""
+    def run(self, name, cpu_leg, dump_dir=None):
+        """Times workload `name`: W warm-up steps, then exactly K steps between fences; returns its record (rank 0) or None.
+        `dump_dir`: where the outputs of the last timed step go (--dump-outputs; the top-level workload only)."""
         torch, dist, eng, ecgpu, args = self.torch, self.dist, self.eng, self.ecgpu, self.args
         world, rank, device = self.world, self.rank, self.device
         wl = WORKLOADS[name]
@@ -594,6 +617,10 @@ class Bench:
             eng.synchronize()            # waits for the queue and raises if any queued batch failed its input checks
         self.fence()
         elapsed = time.perf_counter() - t0
+        if dump_dir and rank == 0:
+            o, f = lane_out[nstep[0] % lanes if lanes > 1 else 0]     # the buffers the last timed step wrote
+            outs = {"ecdsa": {"valid": d_ok}, "recover": {"keys": o, "valid": d_ok}}.get(kind, {"points": o, "infinity": f})
+            dump_outputs(torch, dump_dir, n_out, outs)
         if queued:
             if not sharded:
                 read_events()
@@ -602,7 +629,7 @@ class Bench:
             if lanes > 1:
                 eng.set_msm_lanes(1)
             eng.set_async(False)
-            if lanes == 1:
+            if lanes == 1 and args.full:
                 # the queued steps leave ONE sample of the kernel's duration (the HIP events of the last step); five more steps,
                 # outside the timed region and synchronous, give kernel_ms a minimum and a mean to stand on
                 eng.set_timing(True)
@@ -612,7 +639,8 @@ class Bench:
             t = torch.tensor([elapsed], dtype=torch.float64)           # (the control plane is gloo: a host tensor)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        per_rank = self.per_rank_stages(cid, sets[0], n, plan_terms, exchanges[0], d_out, d_inf) if sharded and world > 1 and lanes == 1 else None
+        per_rank = self.per_rank_stages(cid, sets[0], n, plan_terms, exchanges[0], d_out, d_inf) \
+            if args.full and sharded and world > 1 and lanes == 1 else None
 
         units_per_step = n_total if kind == "msm" else n * world
         value = units_per_step * args.steps / elapsed
@@ -621,7 +649,7 @@ class Bench:
 
         # ---- parity check of the last timed step (every rank takes part in the MSM's collective sum) ----
         ok = None
-        if not args.no_check:
+        if args.full and not args.no_check:
             if kind in ("msm", "lincomb_ct"):
                 part = device_dot_mod(torch, d_scal, d_s2, ecgpu.GROUP_ORDERS[cid])
                 if world > 1 and kind == "msm":
@@ -683,6 +711,23 @@ class Bench:
                     ok = ok and bytes(w) == bytes(d_sum[0].cpu().numpy()) and int(wf[0]) == int(d_sf[0].item())
         if rank != 0:
             return None
+        rec = {
+            "metric": wl["metric"], "value": value, "unit": wl["unit"], "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
+            "scaling": wl["scaling"], "vs_baseline": None, "dtype": "u32 limbs (v_mad_u64_u32)", "data": "synthetic",
+            "config": {"workload": name, "curve": wl["curve"], "units_per_gpu": n, "units_total": units_per_step,
+                       "window_bits": args.window or "default", "parallelism": "shard%d" % world,
+                       **({"exchange": self.exchange_kind, "exchange_reason": self.exchange_reason} if world > 1 else {}),
+                       **({"dry_run": "ranks share one GPU, %s exchange" % self.backend} if os.environ.get("ECGPU_BENCH_SHARE_GPU") else {})},
+        }
+        rec["config"]["input_sets"] = nsets
+        if wl.get("form"):
+            rec["config"]["form"] = wl["form"]
+        if kind in ("fixed", "ecdsa", "recover"):
+            ti = eng.base_table_info(cid)               # the generator table these steps read (built before the timed region)
+            rec["table"] = {"window_bits": ti["window_bits"], "bytes": ti["bytes"], "build_ms": round(ti["build_ms"], 2), "policy": "eager"}
+        if not args.full:
+            return rec
 
         kernel_ms = float(np.mean(main_ms)) if main_ms else None
         kernel_ms_min = float(np.min(main_ms)) if main_ms else None
@@ -705,14 +750,7 @@ class Bench:
             traffic = (rc["fetch_bytes"] + rc["write_bytes"]) * scale if rc.get("fetch_bytes") is not None else None
             basis = rc["source"] + ("" if scale == 1 and not args.window else " (scaled from %d units per launch)" % rc["units_per_launch"])
         hbm_gbps = wl["bytes_per_unit"] * n / ksec / 1e9 if ksec else None
-        rec = {
-            "metric": wl["metric"], "value": value, "unit": wl["unit"], "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True,
-            "scaling": wl["scaling"], "vs_baseline": None, "dtype": "u32 limbs (v_mad_u64_u32)", "data": "synthetic",
-            "config": {"workload": name, "curve": wl["curve"], "units_per_gpu": n, "units_total": units_per_step,
-                       "window_bits": args.window or "default", "parallelism": "shard%d" % world,
-                       **({"exchange": self.exchange_kind, "exchange_reason": self.exchange_reason} if world > 1 else {}),
-                       **({"dry_run": "ranks share one GPU, %s exchange" % self.backend} if os.environ.get("ECGPU_BENCH_SHARE_GPU") else {})},
+        rec.update({
             "calls": "%d %s in flight (ecgpu_set_async + ecgpu_set_msm_lanes), drained inside the timed region; kernel_ms = the last "
                      "accumulation kernel with the other lanes' kernels beside it" % (lanes, "sharded steps" if sharded else "MSMs") if lanes > 1
                      else "queued (ecgpu_set_async), drained inside the timed region; kernel_ms = mean (kernel_ms_min: minimum) over the HIP "
@@ -739,15 +777,9 @@ class Bench:
                                  "measured_frac": traffic / ksec / 1e9 / HBM_PEAK_GBPS if traffic and ksec else None}},
             "stage_ms": {k: float(np.mean(v)) for k, v in stages.items()},
             "check_vs_oracle": ok,
-        }
-        rec["config"]["input_sets"] = nsets
-        if wl.get("form"):
-            rec["config"]["form"] = wl["form"]
+        })
         if per_rank:
             rec["per_rank"] = per_rank
-        if kind in ("fixed", "ecdsa", "recover"):
-            ti = eng.base_table_info(cid)               # the generator table these steps read (built before the timed region)
-            rec["table"] = {"window_bits": ti["window_bits"], "bytes": ti["bytes"], "build_ms": round(ti["build_ms"], 2), "policy": "eager"}
         if cpu_leg:
             ns = min(n, 1 << 17 if kind in ("fixed", "msm", "lincomb_ct") else 1 << 14)
             s_host = d_scal[:ns].cpu().numpy().reshape(-1)
@@ -982,7 +1014,10 @@ def main():
     ap.add_argument("--n", type=int, default=0, help="override units per GPU (msm: total terms); implies a single workload")
     ap.add_argument("--window", type=int, default=0, help="fixed-base / Pippenger window bits override")
     ap.add_argument("--sets", type=int, default=4, help="independently seeded input sets per workload, one per step in turn (default 4)")
-    ap.add_argument("--check", action="store_true", help="(default) verify the last step of every workload against the oracle")
+    ap.add_argument("--full", action="store_true",
+                    help="also the check against the oracle, the roofline, the CPU baseline and (without --only) the other GPU configs and extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--check", action="store_true", help="(the default of --full) verify the last step of every workload against the oracle")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--sync-calls", action="store_true", help="fixed / variable base: one synchronous call per step instead of the queued calls")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -991,6 +1026,8 @@ def main():
                     help="BASELINE configs[0] alone: 1024 k256 generator multiplications on the CPU reference path (no GPU needed)")
     ap.add_argument("--group-msm-child", type=int, default=0, help=argparse.SUPPRESS)     # internal: see group_msm_in_child
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.group_msm_child:
         print(json.dumps(group_msm_child_main(args)), flush=True)
         return None
@@ -1001,9 +1038,17 @@ def main():
 
     b = Bench(args)
     top = args.only or "fixed_k256"
+    if not args.full:
+        rec = b.run(top, False, args.dump_outputs)
+        if rec is not None:
+            print(json.dumps(rec), flush=True)
+        b.close()
+        if _SIGN_POOL is not None:
+            _SIGN_POOL.shutdown()
+        return rec
     cpu_leg = not args.no_cpu_baseline and b.world == 1          # the CPU leg is timed at N = 1 only
     single = bool(args.only or args.n or args.window)
-    rec = b.run(top, cpu_leg)
+    rec = b.run(top, cpu_leg, args.dump_outputs)
     subs = [] if single else [x for x in DEFAULT_SUBS if b.world == 1 or x != "msm_k256_2p21"]
     full = {}
     for name in subs:

@@ -9,7 +9,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sizes = [int(a) for a in sys.argv[1:]] or [21, 24]
-BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--only", "msm_k256", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"]
+BENCH = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only", "msm_k256", "--steps", "20", "--warmup", "3", "--no-cpu-baseline"]
 
 
 def line(out):

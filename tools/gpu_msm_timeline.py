@@ -13,7 +13,7 @@ lg = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 out = "/tmp/msm_timeline_%d" % lg
 env = dict(os.environ, TMPDIR="/tmp")
 cmd = ["rocprofv3", "--kernel-trace", "--output-format", "csv", "-d", out, "-o", "t", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-       "--only", "msm_k256", "--n", str(1 << lg), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+       "--full", "--only", "msm_k256", "--n", str(1 << lg), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
 subprocess.run(cmd, env=env, cwd="/tmp", capture_output=True, text=True, timeout=600)
 rows = []
 for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True):

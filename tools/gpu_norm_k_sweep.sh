@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export ECGPU_TOOL_LIB=$PWD/elliptic-curves_amd/lib/libecgpu_knobs.so
 for k in 16 8 10 12 14 16 20 24 32 16; do
-  ECGPU_NORM_K=$k python bench.py --only fixed_k256 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  ECGPU_NORM_K=$k python bench.py --full --only fixed_k256 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 r = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('NORM_K=$k ms_per_step', round(r['ms_per_step'], 4), r['check_vs_oracle'], {k: round(v, 4) for k, v in r['stage_ms'].items()})"
