@@ -633,6 +633,10 @@ class Engine:
     def msm_parts_bytes(self, curve, plan_terms):
         return int(self._lib.ecgpu_msm_parts_bytes(self._ctx, curve, ctypes.c_size_t(plan_terms)))
 
+    def msm_plan_window(self, curve, plan_terms):
+        """The window width (bits) of the MSM plan for `plan_terms` terms (the pinned one after set_msm_window)."""
+        return int(self._lib.ecgpu_msm_plan_window(self._ctx, curve, ctypes.c_size_t(plan_terms)))
+
     def msm_parts_dev(self, curve, d_scalars, d_points_xy, d_points_inf, n, plan_terms, d_parts):
         self._chk(self._lib.ecgpu_msm_parts_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xy), _dp(d_points_inf),
                                                 ctypes.c_size_t(n), ctypes.c_size_t(plan_terms), _dp(d_parts)))

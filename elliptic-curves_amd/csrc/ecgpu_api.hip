@@ -921,8 +921,8 @@ int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const
         // stream and workspace, ordered after what the context's stream holds now (the inputs), beside the exchange and the
         // combining half of the previous one, which the caller keeps on the context's stream:
         //     parts(i) -> lane i % L      ecgpu_msm_parts_join_dev(d_parts(i - 1)); all-gather(i - 1); ecgpu_msm_finish_dev(i - 1)
-        // d_parts belongs to the lane until ecgpu_msm_parts_join_dev(d_parts) (the context's stream then waits for it) or
-        // ecgpu_synchronize.
+        // d_parts belongs to the lane until ecgpu_msm_parts_join_dev(d_parts) or an ecgpu_msm_finish_dev that reads it (the
+        // context's stream then waits for it), or ecgpu_synchronize.
         ecgpu_ctx::MsmLane* lp = nullptr;
         if ((rc = next_lane(ctx, plan.workspace_bytes, &lp)) != ECGPU_OK) return rc;
         ecgpu_ctx::MsmLane& l = *lp;
@@ -958,9 +958,18 @@ int msm_finish_dev(ecgpu_ctx* ctx, const void* d_parts_all, int nranks, size_t p
     MsmPlan plan = msm_plan<C>(0, c, msm_use_glv<C>(plan_terms));   // only c, nwin and nparts matter here
     if ((rc = ensure(ctx, ctx->proj, 3 * NS * 4)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->bases, (size_t)plan.nwin * 3 * NS * 4)) != ECGPU_OK) return rc;
-    // With local halves in flight on lanes this call does NOT wait for them (that is the point of the lanes): it reads d_parts_all,
-    // which the caller's exchange produced on this stream after ecgpu_msm_parts_join_dev, and scratch of its own.
+    // With local halves in flight on lanes this call does not wait for all of them (that is the point of the lanes), only for those
+    // whose record lies inside d_parts_all: the one-rank form passes its own record, and a caller may skip the join when no exchange
+    // of its own reads the record.  Joined records (parts_out cleared) cost nothing here.
     if (ctx->async && ctx->msm_lanes > 1) {          // (nor does it touch the timing marks: ecgpu_last_timing keeps reading the last lane's)
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(d_parts_all), hi = lo + (size_t)nranks * plan.parts_bytes;
+        for (auto& l : ctx->lane) {
+            const uintptr_t p = reinterpret_cast<uintptr_t>(l.parts_out);
+            if (l.s && l.ev_done && l.parts_out && p >= lo && p < hi) {
+                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.ev_done, 0));
+                l.parts_out = nullptr;
+            }
+        }
         launch_msm_finish<C>(plan, ctx->stream, (const uint32_t*)d_parts_all, nranks, (uint32_t*)ctx->bases.p, (uint32_t*)ctx->proj.p,
                              (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);
         return finish(ctx);

@@ -1387,7 +1387,7 @@ MsmPlan msm_plan(size_t n, int force_c, bool glv) {
             if (bb > MSM_SORTP_MAX_BITS_B) bb = MSM_SORTP_MAX_BITS_B;
             bool packed = bb >= 1 && p.c - 1 - bb <= MSM_SORTP_MAX_BITS_A;
             // k_msm_prepare keeps the level-A histogram of every window in LDS (nwin * npart words) and is launched without the
-            // large-LDS attribute: with 9 level-A bits (more than 2^24 entries per window) the 33 windows of p521 would need 67.6 KB
+            // large-LDS attribute: with 9 level-A bits (more than 2^24 entries per window) the 34 windows of p521 would need 68 KiB
             // — such a plan keeps the unpacked form with its 8 level-A bits
             packed = packed && (size_t)p.nwin * (p.nb >> bb) * 4 <= (size_t)64 * 1024;
             if (const char* e = knob("ECGPU_MSM_SORT_PACKED")) packed = packed && atoi(e) != 0;   // 0: the round-3 kernels (A/B runs)

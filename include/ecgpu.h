@@ -297,7 +297,9 @@ int ecgpu_msm_parts_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const 
  * `d_parts`; until then the record belongs to its lane.  A no-op for a record written on the context's own stream.  A lane keeps
  * track of ONE record: a local half that is still un-joined when its lane comes around again (more halves in flight than lanes) is
  * joined by that call — correct, but the context's stream then waits for it.
- * ecgpu_msm_finish_dev does not wait for local halves in flight.  One MSM alone gains nothing from lanes. */
+ * ecgpu_msm_finish_dev waits only for the local halves in flight whose records lie inside its nranks records at d_parts_all
+ * (the one-rank form, parts -> finish on the same record, needs no join); ecgpu_msm_parts_join_dev is still required before the
+ * caller's own exchange reads a record.  One MSM alone gains nothing from lanes. */
 int ecgpu_msm_parts_join_dev(ecgpu_ctx *ctx, const void *d_parts);
 /* d_parts_all: nranks consecutive parts records (the all-gather's output). */
 int ecgpu_msm_finish_dev(ecgpu_ctx *ctx, int curve, const void *d_parts_all, int nranks, size_t plan_terms, void *d_out_xy,

@@ -29,6 +29,33 @@ def rand_scalars(curve_id, n, seed):
     return oracle_lib.scalar_reduce(curve_id, rng.integers(0, 256, n * L, dtype=np.uint8))
 
 
+def fast_scalars(c, n, seed):
+    """n uniformly random canonical scalars as an (n, L) uint8 array.  The orders of k256, p256 and p384 start with
+    32 one bits, so clearing one bit of an all-ones top word (probability 2^-32) keeps every value below n."""
+    assert c.n >> (8 * c.L - 32) == 0xFFFFFFFF
+    b = np.random.default_rng(seed).integers(0, 256, (n, c.L), dtype=np.uint8)
+    top = (b[:, 0] == 255) & (b[:, 1] == 255) & (b[:, 2] == 255) & (b[:, 3] == 255)
+    b[top, 3] = 254
+    return b
+
+
+def dot_mod(k, s, mod):
+    """sum_i k_i * s_i mod `mod` for two (n, L) big-endian byte arrays: 16-bit limbs of k against 8-bit limbs of s in
+    float64 matrix products (every partial sum stays below 2^53, so the arithmetic is exact)."""
+    n, L = k.shape
+    total = 0
+    step = 1 << 19
+    for lo in range(0, n, step):
+        kc = k[lo:lo + step].astype(np.float64)
+        k16 = kc[:, 0::2] * 256.0 + kc[:, 1::2]                       # limb j has weight 2^(16 (L/2 - 1 - j))
+        m = k16.T @ s[lo:lo + step].astype(np.float64)                 # (L/2, L), entries < 2^24 * 2^19
+        for a in range(L // 2):
+            wa = 16 * (L // 2 - 1 - a)
+            for b in range(L):
+                total += int(m[a, b]) << (wa + 8 * (L - 1 - b))
+    return total % mod
+
+
 def edge_scalars(c):
     ks = [0, 1, 2, c.n - 1, c.n - 2, (c.n - 1) // 2, 2 ** 128, 2 ** (8 * c.L - 1) % c.n, int("80" * c.L, 16) % c.n,
           int("7f" * c.L, 16) % c.n, 0xFFFF, 0x10000, 0x8000]

@@ -7,7 +7,7 @@ import pytest
 
 import oracle_lib
 import pyec
-from gpu_common import ecgpu_module, scalars_to_int_sum
+from gpu_common import dot_mod, ecgpu_module, fast_scalars, rand_scalars, scalars_to_int_sum
 
 @pytest.fixture(scope="module")
 def eng():
@@ -17,33 +17,6 @@ def eng():
     e.close()
 
 
-def fast_scalars(c, n, seed):
-    """n uniformly random canonical scalars as an (n, L) uint8 array.  The orders of k256, p256 and p384 start with
-    32 one bits, so clearing one bit of an all-ones top word (probability 2^-32) keeps every value below n."""
-    assert c.n >> (8 * c.L - 32) == 0xFFFFFFFF
-    b = np.random.default_rng(seed).integers(0, 256, (n, c.L), dtype=np.uint8)
-    top = (b[:, 0] == 255) & (b[:, 1] == 255) & (b[:, 2] == 255) & (b[:, 3] == 255)
-    b[top, 3] = 254
-    return b
-
-
-def dot_mod(k, s, mod):
-    """sum_i k_i * s_i mod `mod` for two (n, L) big-endian byte arrays: 16-bit limbs of k against 8-bit limbs of s in
-    float64 matrix products (every partial sum stays below 2^53, so the arithmetic is exact)."""
-    n, L = k.shape
-    total = 0
-    step = 1 << 19
-    for lo in range(0, n, step):
-        kc = k[lo:lo + step].astype(np.float64)
-        k16 = kc[:, 0::2] * 256.0 + kc[:, 1::2]                       # limb j has weight 2^(16 (L/2 - 1 - j))
-        m = k16.T @ s[lo:lo + step].astype(np.float64)                 # (L/2, L), entries < 2^24 * 2^19
-        for a in range(L // 2):
-            wa = 16 * (L // 2 - 1 - a)
-            for b in range(L):
-                total += int(m[a, b]) << (wa + 8 * (L - 1 - b))
-    return total % mod
-
-
 def test_dot_mod_helper_is_exact():
     c = pyec.K256
     k, s = fast_scalars(c, 3000, 1), fast_scalars(c, 3000, 2)
@@ -51,6 +24,22 @@ def test_dot_mod_helper_is_exact():
     s[:7] = 255                                                       # worst-case limbs
     want = sum(int.from_bytes(bytes(k[i]), "big") * int.from_bytes(bytes(s[i]), "big") for i in range(3000)) % c.n
     assert dot_mod(k, s, c.n) == want
+
+
+def test_dot_mod_helper_is_exact_at_66_byte_scalars():
+    """p521 (L = 66: 33 sixteen-bit limbs of k against 66 bytes of s): a partial sum of one 2^19-term step is below
+    2^16 * 2^8 * 2^19 = 2^43, so the float64 products stay exact.  Random scalars with worst-case rows, and the worst case
+    itself: a whole step plus a few terms of all-ones bytes, against its closed form."""
+    c = pyec.CURVES["p521"]
+    L = c.L
+    k, s = rand_scalars(c.cid, 3000, 1).reshape(-1, L), rand_scalars(c.cid, 3000, 2).reshape(-1, L)
+    k[:7] = 255
+    s[:7] = 255                                                       # worst-case limbs
+    want = sum(int.from_bytes(bytes(k[i]), "big") * int.from_bytes(bytes(s[i]), "big") for i in range(3000)) % c.n
+    assert dot_mod(k, s, c.n) == want
+    rows = (1 << 19) + 3
+    ones = np.full((rows, L), 255, np.uint8)
+    assert dot_mod(ones, ones, c.n) == ((1 << (8 * L)) - 1) ** 2 * rows % c.n
 
 
 def _msm_dev(eng, cid, L, d_k, d_p, n, koff=0):
