@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "ecgpu_lincomb_ct", "ecgpu_lincomb_ct_dev", "ecgpu_msm_compressed", "ecgpu_msm_compressed_dev",
     "ecgpu_batch_mul_compressed", "ecgpu_batch_mul_compressed_dev", "ecgpu_wipe", "ecgpu_group_exchange_reason",
     "ecgpu_set_table_policy", "ecgpu_set_table_budget", "ecgpu_base_table_info", "ecgpu_group_set_exchange_timeout", "ecgpu_group_set_exchange", "ecgpu_msm_parts_join_dev",
+    "ecgpu_batch_mul_ct_xyz", "ecgpu_batch_mul_ct_xyz_dev", "ecgpu_lincomb_ct_xyz", "ecgpu_lincomb_ct_xyz_dev",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -161,6 +162,12 @@ def _need(what, a, nbytes):
     """Host buffers are handed to C as bare pointers: a short one would be read or written past its end."""
     if a is not None and a.size != nbytes:
         raise EcgpuError(ERR_ARG, "%s holds %d bytes, expected %d" % (what, a.size, nbytes))
+
+
+def _need_ct_xyz(constant_time):
+    if not constant_time:
+        raise EcgpuError(ERR_ARG, "projective (X || Y || Z) records are taken by the uniform-schedule entry points only "
+                                  "(constant_time=True); for the variable-time ones normalise first (batch_normalize)")
 
 
 def _dp(t):
@@ -383,6 +390,32 @@ class Engine:
         out = np.zeros(2 * L, np.uint8)
         inf = np.zeros(1, np.uint8)
         self._chk(self._lib.ecgpu_lincomb_ct(self._ctx, curve, _hp(s), _hp(p), _hp(pi), ctypes.c_size_t(n), _hp(out), _hp(inf)))
+        return out, int(inf[0])
+
+    def mul_xyz(self, curve, scalars, points_xyz, *, constant_time):
+        """k_i * P_i for projective points P_i = X_i || Y_i || Z_i (3L bytes each, Z = 0 the identity), with no `to_affine` in
+        front.  constant_time=True: the uniform-schedule entry point ecgpu_batch_mul_ct_xyz (`Mul<Scalar>` on a
+        `ProjectivePoint`).  The library has no variable-time entry point for projective records: constant_time=False raises
+        (normalise with batch_normalize and call `mul`), and the argument has no default until it has one."""
+        _need_ct_xyz(constant_time)
+        L = _field_bytes(curve)
+        s, p = _host(scalars), _host(points_xyz)
+        n = s.size // L
+        _need("scalars", s, n * L); _need("points_xyz", p, n * 3 * L)
+        out = np.zeros(n * 2 * L, np.uint8)
+        inf = np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_batch_mul_ct_xyz(self._ctx, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
+        return out, inf
+
+    def lincomb_ct_xyz(self, curve, scalars, points_xyz):
+        """sum_i k_i P_i over projective points (X || Y || Z records) by ecgpu_lincomb_ct_xyz: `lincomb` in its constant-time form."""
+        L = _field_bytes(curve)
+        s, p = _host(scalars), _host(points_xyz)
+        n = s.size // L
+        _need("scalars", s, n * L); _need("points_xyz", p, n * 3 * L)
+        out = np.zeros(2 * L, np.uint8)
+        inf = np.zeros(1, np.uint8)
+        self._chk(self._lib.ecgpu_lincomb_ct_xyz(self._ctx, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
         return out, int(inf[0])
 
     def lincomb_compressed(self, curve, scalars, points_x, points_tag):
@@ -620,6 +653,15 @@ class Engine:
     def lincomb_ct_dev(self, curve, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf):
         self._chk(self._lib.ecgpu_lincomb_ct_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xy), _dp(d_points_inf),
                                                  ctypes.c_size_t(n), _dp(d_out_xy), _dp(d_out_inf)))
+
+    def mul_xyz_dev(self, curve, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf=None, *, constant_time):
+        _need_ct_xyz(constant_time)
+        self._chk(self._lib.ecgpu_batch_mul_ct_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
+                                                       _dp(d_out_xy), _dp(d_out_inf)))
+
+    def lincomb_ct_xyz_dev(self, curve, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf):
+        self._chk(self._lib.ecgpu_lincomb_ct_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
+                                                     _dp(d_out_xy), _dp(d_out_inf)))
 
     def lincomb_compressed_dev(self, curve, d_scalars, d_points_x, d_points_tag, n, d_out_xy, d_out_inf):
         self._chk(self._lib.ecgpu_msm_compressed_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_x), _dp(d_points_tag),

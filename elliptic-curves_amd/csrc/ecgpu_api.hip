@@ -663,9 +663,10 @@ int mul_base_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out
     return rc;
 }
 
+// xyz: d_points_xy holds projective records X || Y || Z (k_xyz_mul_ct) and d_points_inf is unused
 template <class C>
 int mul_var_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_points_xy, const void* d_points_inf, size_t n,
-                   void* d_out_xy, void* d_out_inf) {
+                   void* d_out_xy, void* d_out_inf, bool xyz = false) {
     constexpr int NS = Field<C>::NS;
     if (n == 0) return ECGPU_OK;
     int rc;
@@ -676,8 +677,12 @@ int mul_var_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_points_x
     if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
     if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
     record(ctx, 0);
-    launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
-                          (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    if (xyz)
+        launch_xyz_mul_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, n, (uint32_t*)ctx->vtab.p, tstride,
+                             (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    else
+        launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
+                              (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     record(ctx, 1);
     if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
     record(ctx, 2);
@@ -834,9 +839,10 @@ int msm_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void*
 // mul.rs:84-98 -> :112-163): one uniform-schedule multiplication per term (k_var_base_ct: the reference's table, digits and
 // additions for that term) and a tree of complete additions over the products, 256 per workgroup and level.  The reference
 // interleaves the terms on one accumulator (Straus); the group element is the same and the schedule here depends on n only.
+// xyz: d_xy holds projective records X || Y || Z (k_xyz_mul_ct) and d_inf is unused
 template <class C>
 int lincomb_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy,
-                   void* d_out_inf) {
+                   void* d_out_inf, bool xyz = false) {
     constexpr int NS = Field<C>::NS, WB = WireBytes<C>::value;
     int rc;
     if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
@@ -852,8 +858,12 @@ int lincomb_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, cons
     if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->prefix, ((n + BLOCK - 1) / BLOCK + 1) * 3 * NS * 4)) != ECGPU_OK) return rc;
     record(ctx, 0);
-    launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n,
-                          (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    if (xyz)
+        launch_xyz_mul_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, n, (uint32_t*)ctx->vtab.p, tstride,
+                             (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    else
+        launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n,
+                              (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     record(ctx, 3);
     launch_proj_sum<C>(ctx->stream, (uint32_t*)ctx->proj.p, n, (uint32_t*)ctx->prefix.p);
     record(ctx, 1);
@@ -1578,6 +1588,16 @@ int ecgpu_batch_mul_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, con
     });
 }
 
+int ecgpu_batch_mul_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
+                               void* d_out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (n && (!d_scalars || !d_points_xyz || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xyz) || !aligned16(d_out_xy)))
+        return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) {
+        return mul_var_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
+    });
+}
+
 int ecgpu_msm_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, const void* d_points_inf,
                   size_t n, void* d_out_xy, void* d_out_inf) {
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
@@ -1595,6 +1615,16 @@ int ecgpu_lincomb_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const
     if (n && (!d_scalars || !d_points_xy || !aligned16(d_scalars) || !aligned16(d_points_xy))) return arg_error(ctx, __func__);
     return dispatch(curve, [&](auto c) {
         return lincomb_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
+    });
+}
+
+int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
+                             void* d_out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
+    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) {
+        return lincomb_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
     });
 }
 
@@ -1947,43 +1977,52 @@ int ecgpu_batch_mul_base_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* sc
     return download(ctx, out_tag, ctx->out1, n);
 }
 
-static int batch_mul_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
-                          size_t n, uint8_t* out_xy, uint8_t* out_inf, bool ct, const char* fn) {
-    const auto dev = ct ? ecgpu_batch_mul_ct_dev : ecgpu_batch_mul_dev;
+// the host-pointer batch multiplication over either point record: affine x || y (+ optional identity flags) for
+// ecgpu_batch_mul[_ct], projective X || Y || Z (3L bytes, no flags) for ecgpu_batch_mul_ct_xyz
+static int batch_mul_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points, const uint8_t* points_inf,
+                          size_t n, uint8_t* out_xy, uint8_t* out_inf, bool ct, bool xyz, const char* fn) {
+    const auto dev = [&](const void* k, const void* p, const void* pi, size_t m, void* o, void* oi) {
+        if (xyz) return ecgpu_batch_mul_ct_xyz_dev(ctx, curve, k, p, m, o, oi);
+        return ct ? ecgpu_batch_mul_ct_dev(ctx, curve, k, p, pi, m, o, oi) : ecgpu_batch_mul_dev(ctx, curve, k, p, pi, m, o, oi);
+    };
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
     SyncScope sync_scope(ctx);
     if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
     size_t L = ecgpu_field_bytes(curve);
     if (!L) return curve_error(ctx, fn);
-    if (n && (!scalars || !points_xy || !out_xy)) return arg_error(ctx, fn);
+    if (n && (!scalars || !points || !out_xy)) return arg_error(ctx, fn);
+    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
     CtWipe wipe(ctx, ct ? WIPE_STAGING : 0);
     int rc;
     if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_xy, &ctx->in1, 2 * L}, {points_inf, &ctx->in2, 1}},
+        return pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
                          {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L,
-                                                        points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m,
-                                                        (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
+                             return dev((uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
+                                        points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, (uint8_t*)ctx->out0.p + off * 2 * L,
+                                        (uint8_t*)ctx->out1.p + off);
                          });
     if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
+    if ((rc = upload(ctx, ctx->in1, points, n * PB)) != ECGPU_OK) return rc;
     if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
-                                  ctx->out1.p)) != ECGPU_OK)
-        return rc;
+    if ((rc = dev(ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
     if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
     return download(ctx, out_inf, ctx->out1, n);
 }
 
 int ecgpu_batch_mul(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
                     uint8_t* out_xy, uint8_t* out_inf) {
-    return batch_mul_host(ctx, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, false, __func__);
+    return batch_mul_host(ctx, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, false, false, __func__);
 }
 int ecgpu_batch_mul_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
                        uint8_t* out_xy, uint8_t* out_inf) {
-    return batch_mul_host(ctx, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, true, __func__);
+    return batch_mul_host(ctx, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, true, false, __func__);
+}
+
+int ecgpu_batch_mul_ct_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
+                           uint8_t* out_inf) {
+    return batch_mul_host(ctx, curve, scalars, points_xyz, nullptr, n, out_xy, out_inf, true, true, __func__);
 }
 
 int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
@@ -2052,6 +2091,25 @@ int ecgpu_lincomb_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const ui
     if ((rc = ecgpu_lincomb_ct_dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
                                    ctx->out1.p)) != ECGPU_OK)
         return rc;
+    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
+    return download(ctx, out_inf, ctx->out1, 1);
+}
+
+int ecgpu_lincomb_ct_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
+                         uint8_t* out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    SyncScope sync_scope(ctx);
+    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
+    size_t L = ecgpu_field_bytes(curve);
+    if (!L) return curve_error(ctx, __func__);
+    if (!out_xy || (n && (!scalars || !points_xyz))) return arg_error(ctx, __func__);
+    CtWipe wipe(ctx, WIPE_STAGING);
+    int rc;
+    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
+    if ((rc = upload(ctx, ctx->in1, points_xyz, n * 3 * L)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
+    if ((rc = ecgpu_lincomb_ct_xyz_dev(ctx, curve, ctx->in0.p, ctx->in1.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
     if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
     return download(ctx, out_inf, ctx->out1, 1);
 }

@@ -36,6 +36,17 @@ __device__ __forceinline__ uint32_t ct_load_point(Proj<C>* p, const uint8_t* xy,
     return ((int)ok | (int)ident) ? 0u : CT_FLAG_BAD_POINT;
 }
 
+// projective record X || Y || Z -> the point and its verdict (ct_xyz_point); the three coordinates are read like any other
+template <class C>
+__device__ __forceinline__ uint32_t ct_load_xyz(Proj<C>* p, const uint8_t* xyz, size_t i, const Fe<C::NL>& b) {
+    constexpr int WB = WireBytes<C>::value;
+    uint32_t cx[C::N], cy[C::N], cz[C::N];
+    load_wire<C>(cx, xyz + i * (3 * WB));
+    load_wire<C>(cy, xyz + i * (3 * WB) + WB);
+    load_wire<C>(cz, xyz + i * (3 * WB) + 2 * WB);
+    return ct_xyz_point<C>(p, cx, cy, cz, b);
+}
+
 // out[i] = k[i] * P[i]; one lane per element, the table [P..8P] (projective) in the lane's slot of the HBM scratch that
 // the variable-time kernel uses too (ecgpu_var.h: [wave][entry][row][lane], every access a coalesced 256-byte row)
 template <class C>
@@ -52,6 +63,28 @@ k_var_base_ct(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ p
         uint32_t f = ct_load_scalar<C>(k, scalars, i);
         Proj<C> p;
         f |= ct_load_point<C>(&p, points_xy, points_inf, i, b);
+        flags[i] = (uint8_t)f;
+        store_proj<C>(proj_out, i, var_base_mul_ct<C>(p, k, b, io));
+    }
+}
+
+// the same with projective records (ecgpu_batch_mul_ct_xyz, ecgpu_lincomb_ct_xyz): ct_table_build starts from any (X : Y : Z)
+// with complete additions, so P goes in as it is read, with no inversion.  (Named so that no name of the kernels above is a
+// part of it: tools/ct_isa_check.py selects kernels by substring.)
+template <class C>
+__global__ void __launch_bounds__(BLOCK, 2)
+k_xyz_mul_ct(const uint8_t* __restrict__ scalars, const uint8_t* __restrict__ points_xyz, size_t n, uint32_t* __restrict__ tab,
+             size_t tstride, uint32_t* __restrict__ proj_out, uint8_t* __restrict__ flags) {
+    using G = Group<C>;
+    constexpr int N = C::N;
+    const size_t slot = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // < tstride
+    const Fe<C::NL> b = G::curve_b();
+    VarTabHbm<C> io{tab + (slot / 64) * (size_t)(8 * VarTabHbm<C>::ROWS * 64) + (slot % 64)};
+    for (size_t i = slot; i < n; i += tstride) {
+        uint32_t k[N];
+        uint32_t f = ct_load_scalar<C>(k, scalars, i);
+        Proj<C> p;
+        f |= ct_load_xyz<C>(&p, points_xyz, i, b);
         flags[i] = (uint8_t)f;
         store_proj<C>(proj_out, i, var_base_mul_ct<C>(p, k, b, io));
     }

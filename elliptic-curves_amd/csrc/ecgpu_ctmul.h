@@ -100,6 +100,39 @@ ECGPU_HD Proj<C> ct_sel_proj(bool flag, const Proj<C>& a, const Proj<C>& b) {
     return r;
 }
 
+// A homogeneous projective record (X : Y : Z), x = X/Z, y = Y/Z (the reference's `ProjectivePoint`, k256 projective.rs:40-45,
+// primeorder projective.rs:49-53), canonical words -> the point, (0 : 1 : 0) when Z = 0 whatever X and Y are (`to_affine`,
+// k256 projective.rs:64-69).  The verdict: X, Y, Z < p, and Y^2 Z = X^3 + a X Z^2 + b Z^3 unless Z = 0 — what `to_affine`
+// followed by `AffinePoint::from_coordinates` (primeorder/src/affine.rs:100-109) accepts.  Both are computed for every
+// record with `&` / `|` and the identity is picked under a mask: no branch on the record's contents.
+template <class C>
+ECGPU_HD uint32_t ct_xyz_point(Proj<C>* p, const uint32_t* cx, const uint32_t* cy, const uint32_t* cz, const Fe<C::NL>& b) {
+    using F = Field<C>;
+    using G = Group<C>;
+    const bool in_range = (int)!mp_geq<C::N>(cx, C::P) & (int)!mp_geq<C::N>(cy, C::P) & (int)!mp_geq<C::N>(cz, C::P);
+    Proj<C> q;
+    q.x = F::from_canonical(cx).e;
+    q.y = F::from_canonical(cy).e;
+    q.z = F::from_canonical(cz).e;
+    const auto X = G::m(q.x), Y = G::m(q.y), Z = G::m(q.z);
+    const auto Z2 = F::sqr(Z);
+    const auto bZ3 = F::mul(G::m(b), F::mul(Z2, Z));
+    const auto lhs = F::mul(F::sqr(Y), Z);
+    const auto X3 = F::mul(F::sqr(X), X);
+    bool on;
+    if constexpr (C::A_IS_ZERO) {
+        on = F::eq(lhs, F::add(X3, bZ3));
+    } else if constexpr (GenericA<C>::value) {
+        on = F::eq(lhs, F::add(F::add(X3, F::mul(G::curve_a(), F::mul(X, Z2))), bZ3));
+    } else {
+        const auto XZ2 = F::mul(X, Z2);
+        on = F::eq(lhs, F::add(F::norm(F::sub(X3, F::add(F::dbl(XZ2), XZ2))), bZ3));
+    }
+    const bool zero = F::is_zero(Z);
+    *p = ct_sel_proj<C>(zero, G::identity(), q);
+    return ((int)in_range & ((int)zero | (int)on)) ? 0u : CT_FLAG_BAD_POINT;
+}
+
 // |d| and sign of a signed digit without a data-dependent branch (lookup.rs:47-49)
 ECGPU_HD uint32_t ct_abs_digit(int d, bool* neg) {
     const int m = d >> 31;

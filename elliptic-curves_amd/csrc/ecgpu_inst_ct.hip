@@ -17,6 +17,12 @@ template <> void launch_var_base_ct<CurveT>(hipStream_t s, const uint8_t* scalar
                        proj_out, flags);
     hipLaunchKernelGGL(k_ct_flags, dim3(64), dim3(BLOCK), 0, s, (const uint8_t*)flags, n, status);
 }
+template <> void launch_xyz_mul_ct<CurveT>(hipStream_t s, const uint8_t* scalars, const uint8_t* xyz, size_t n, uint32_t* tab, size_t slots,
+                                           uint32_t* proj_out, uint8_t* flags, int* status) {
+    hipLaunchKernelGGL(k_xyz_mul_ct<CurveT>, dim3((unsigned)(slots / BLOCK)), dim3(BLOCK), 0, s, scalars, xyz, n, tab, slots, proj_out,
+                       flags);
+    hipLaunchKernelGGL(k_ct_flags, dim3(64), dim3(BLOCK), 0, s, (const uint8_t*)flags, n, status);
+}
 template <> void launch_fixed_base_ct<CurveT>(hipStream_t s, const uint8_t* scalars, size_t n, const uint32_t* lut, uint32_t* proj_out,
                                               uint8_t* flags, int* status) {
     hipLaunchKernelGGL(k_fixed_base_ct<CurveT>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, scalars, n, lut, proj_out,

@@ -104,6 +104,8 @@ template <class C> void launch_var_base_ct(hipStream_t s, const uint8_t* scalars
                                            uint32_t* tab, size_t slots, uint32_t* proj_out, uint8_t* flags, int* status);
 template <class C> void launch_fixed_base_ct(hipStream_t s, const uint8_t* scalars, size_t n, const uint32_t* lut, uint32_t* proj_out,
                                              uint8_t* flags, int* status);
+template <class C> void launch_xyz_mul_ct(hipStream_t s, const uint8_t* scalars, const uint8_t* xyz, size_t n, uint32_t* tab,
+                                          size_t slots, uint32_t* proj_out, uint8_t* flags, int* status);   // projective records
 
 // ---- group "msm": Pippenger pipeline ----
 template <class C> MsmPlan msm_plan(size_t n, int force_c, bool glv);

@@ -21,10 +21,10 @@
 //! The constant-time entry points (`Mul`, `mul_by_generator`, `diffie_hellman`: primeorder/src/projective.rs:532-557,
 //! 847-886, tables/lookup.rs:43-65, k256/src/ecdh.rs:56-60) have batch forms of their own over the library's
 //! uniform-schedule kernels — `batch_mul`, `batch_mul_by_generator`, `batch_diffie_hellman` below call
-//! `ecgpu_batch_mul_ct` / `ecgpu_batch_mul_base_ct` / `ecgpu_batch_ecdh_ct`: the reference's constant-time algorithm
+//! `ecgpu_batch_mul_ct_xyz` / `ecgpu_batch_mul_base_ct` / `ecgpu_batch_ecdh_ct`: the reference's constant-time algorithm
 //! itself (fixed digit count, every table entry read and one kept under a mask, complete formulas), with no branch and
 //! no address computed from scalar or point data (include/ecgpu.h, "uniform-schedule variants"; tools/ct_isa_check.py).
-//! The constant-time `lincomb` (:484-496; k256 mul.rs:84-98) goes to `ecgpu_lincomb_ct` (`lincomb` below): one
+//! The constant-time `lincomb` (:484-496; k256 mul.rs:84-98) goes to `ecgpu_lincomb_ct_xyz` (`lincomb` below): one
 //! uniform-schedule multiplication per term and a tree of complete additions — never to the bucket method, which is
 //! variable-time by construction.
 //! Memory hygiene on these paths: the wire copies of secret scalars and of shared secrets live in `Zeroizing` buffers here,
@@ -181,6 +181,31 @@ where
     (xy, inf)
 }
 
+/// The homogeneous coordinates (X : Y : Z) of a `ProjectivePoint` as canonical field bytes (`FieldElement::to_bytes`, which
+/// normalises on k256).  The fields are private to the crates (primeorder/src/projective.rs:49-53,
+/// k256/src/arithmetic/projective.rs:40-45): the in-crate patch of INTEGRATION.md adds this accessor.
+pub trait ProjectiveCoordinates<C: GpuCurve>
+where
+    C::FieldBytesSize: ModulusSize,
+{
+    fn xyz_bytes(&self) -> [FieldBytes<C>; 3];
+}
+
+/// Projective points as `X || Y || Z` records (include/ecgpu.h, "projective inputs"): no `to_affine`, no inversion on the CPU.
+fn points_to_wire_xyz<C: GpuCurve>(ps: impl Iterator<Item = Proj<C>>) -> Vec<u8>
+where
+    C::FieldBytesSize: ModulusSize,
+    Proj<C>: ProjectiveCoordinates<C>,
+{
+    let mut xyz = Vec::new();
+    for p in ps {
+        for c in p.xyz_bytes() {
+            xyz.extend_from_slice(c.as_ref());
+        }
+    }
+    xyz
+}
+
 fn point_from_wire<C: GpuCurve>(xy: &[u8], inf: u8) -> Proj<C>
 where
     C::FieldBytesSize: ModulusSize,
@@ -261,19 +286,19 @@ pub mod gpu {
 
     /// `k[i] * P[i]` — batch form of the constant-time `impl Mul<Scalar> for ProjectivePoint`
     /// (primeorder/src/projective.rs:847-886, k256/src/arithmetic/mul.rs:249-274) on the uniform-schedule kernel.
+    /// The points go in as they are, `X || Y || Z` (`ecgpu_batch_mul_ct_xyz`).
     pub fn batch_mul<C: GpuCurve>(terms: &[(Proj<C>, Sc<C>)]) -> Option<Vec<Proj<C>>>
     where
         C::FieldBytesSize: ModulusSize,
         Aff<C>: FromSec1Point<C> + AffineCoordinates<FieldRepr = FieldBytes<C>>,
+        Proj<C>: ProjectiveCoordinates<C>,
     {
         let eng = ENGINE.as_ref()?.lock().ok()?;
         let (n, l) = (terms.len(), field_len::<C>());
         let scalars = secret_scalars_to_wire::<C>(terms.iter().map(|t| t.1));
-        let (pts, pinf) = points_to_wire::<C>(terms.iter().map(|t| t.0));
+        let pts = points_to_wire_xyz::<C>(terms.iter().map(|t| t.0));
         let (mut xy, mut inf) = (Zeroizing::new(vec![0u8; n * 2 * l]), vec![0u8; n]);    // k P for a secret k: wiped on drop
-        check(unsafe {
-            ecgpu_batch_mul_ct(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(), inf.as_mut_ptr())
-        })?;
+        check(unsafe { ecgpu_batch_mul_ct_xyz(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), inf.as_mut_ptr()) })?;
         Some(xy.chunks(2 * l).zip(inf).map(|(c, f)| point_from_wire::<C>(c, f)).collect())
     }
 
@@ -297,20 +322,22 @@ pub mod gpu {
     }
 
     /// `sum_i k[i] * P[i]` — `LinearCombination::lincomb`, the CONSTANT-TIME form (primeorder/src/projective.rs:484-496,
-    /// k256/src/arithmetic/mul.rs:84-98): `ecgpu_lincomb_ct`, one uniform-schedule multiplication per term and a tree of
+    /// k256/src/arithmetic/mul.rs:84-98): `ecgpu_lincomb_ct_xyz`, one uniform-schedule multiplication per term and a tree of
     /// complete additions.  Costs n constant-time multiplications (no bucket method): worth it from a few hundred terms
     /// (`GPU_MIN_TERMS_CT`), where the reference's Straus loop over n per-term tables has left the CPU caches.
+    /// The points go in as they are, `X || Y || Z` (`ecgpu_lincomb_ct_xyz`).
     pub fn lincomb<C: GpuCurve>(terms: &[(Proj<C>, Sc<C>)]) -> Option<Proj<C>>
     where
         C::FieldBytesSize: ModulusSize,
         Aff<C>: FromSec1Point<C> + AffineCoordinates<FieldRepr = FieldBytes<C>>,
+        Proj<C>: ProjectiveCoordinates<C>,
     {
         let eng = ENGINE.as_ref()?.lock().ok()?;
         let (n, l) = (terms.len(), field_len::<C>());
         let scalars = secret_scalars_to_wire::<C>(terms.iter().map(|t| t.1));
-        let (pts, pinf) = points_to_wire::<C>(terms.iter().map(|t| t.0));
+        let pts = points_to_wire_xyz::<C>(terms.iter().map(|t| t.0));
         let (mut xy, mut inf) = (Zeroizing::new(vec![0u8; 2 * l]), 0u8);
-        check(unsafe { ecgpu_lincomb_ct(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(), &mut inf) })?;
+        check(unsafe { ecgpu_lincomb_ct_xyz(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), &mut inf) })?;
         Some(point_from_wire::<C>(&xy, inf))
     }
 

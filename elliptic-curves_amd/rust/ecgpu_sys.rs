@@ -579,6 +579,42 @@ unsafe extern "C" {
         d_out_xy: *mut c_void,
         d_out_inf: *mut c_void,
     ) -> c_int;
+    pub fn ecgpu_batch_mul_ct_xyz(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_batch_mul_ct_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        d_out_xy: *mut c_void,
+        d_out_inf: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_lincomb_ct_xyz(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_lincomb_ct_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        d_out_xy: *mut c_void,
+        d_out_inf: *mut c_void,
+    ) -> c_int;
     pub fn ecgpu_msm_compressed(
         ctx: *mut EcgpuCtx,
         curve: c_int,

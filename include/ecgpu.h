@@ -19,7 +19,9 @@
  *             (primeorder/src/affine.rs:106-112) + optional n-byte identity flags
  *             (`AffinePoint::infinity`, k256/src/arithmetic/affine.rs:45-49); NULL flags = none.
  *             The identity is encoded as x = y = 0 with flag 1 on output.
- *   projective inputs (batch_normalize only): n * 3L bytes X || Y || Z, canonical big-endian.
+ *   projective inputs (ecgpu_batch_normalize, ecgpu_batch_mul_ct_xyz, ecgpu_lincomb_ct_xyz): n * 3L bytes X || Y || Z,
+ *             canonical big-endian, homogeneous (x = X/Z, y = Y/Z: `ProjectivePoint`, k256/src/arithmetic/projective.rs:40-45,
+ *             primeorder/src/projective.rs:49-53); Z = 0 is the identity whatever X and Y are (`to_affine`); no flag array.
  *   ECGPU_BIGN256 (bign-curve256v1, `bignp256`) is the exception to "big-endian": its field elements and scalars travel
  *             LITTLE-endian, as in the reference (`FIELD_ENDIANNESS = LittleEndian`, bignp256/src/lib.rs:102); everything
  *             else about the records is the same.
@@ -46,7 +48,8 @@
  * traffic).  ecgpu_batch_mul_base* and ecgpu_batch_ecdh accept whatever scalars they are given: a caller that passes
  * private keys there has decided that its threat model allows it; the results are the same group elements either way.
  * For secret scalars there are the uniform-schedule entry points ecgpu_batch_mul_base_ct, ecgpu_batch_mul_ct,
- * ecgpu_batch_ecdh_ct and ecgpu_lincomb_ct (below): the reference's constant-time drivers — fixed digit count, every table entry read and one
+ * ecgpu_batch_ecdh_ct and ecgpu_lincomb_ct, and ecgpu_batch_mul_ct_xyz / ecgpu_lincomb_ct_xyz for projective points
+ * (below): the reference's constant-time drivers — fixed digit count, every table entry read and one
  * kept under a mask, complete additions — at 1.2-7x the cost of the variable-time kernels.
  *
  * Threading: a context may be used from one thread at a time (calls serialise on its stream);
@@ -540,6 +543,22 @@ int ecgpu_lincomb_ct(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const ui
                      size_t n, uint8_t *out_xy, uint8_t *out_inf);
 int ecgpu_lincomb_ct_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xy, const void *d_points_inf,
                          size_t n, void *d_out_xy, void *d_out_inf);
+
+/* The same two with projective points: point i is the record X || Y || Z of the wire format above (3L bytes, no flag array),
+ * as the reference's `Mul<Scalar>` and `lincomb` take a `ProjectivePoint`.  For every input the results and the return code
+ * are those of `to_affine` applied to each record followed by ecgpu_batch_mul_ct / ecgpu_lincomb_ct: X, Y or Z >= p, and a
+ * record with Z != 0 and Y^2 Z != X^3 + a X Z^2 + b Z^3, fail the call with ECGPU_ERR_POINT; Z = 0 is the identity.  No
+ * inversion: the per-term table starts from (X : Y : Z) by complete additions (k_xyz_mul_ct), and the verdicts are computed
+ * for every record under the same rule as above — no branch and no address depends on X, Y or Z.  Host-pointer
+ * ecgpu_batch_mul_ct_xyz runs the pipeline of ecgpu_batch_mul_ct from 2^19 points, with 3L-byte records. */
+int ecgpu_batch_mul_ct_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const uint8_t *points_xyz, size_t n, uint8_t *out_xy,
+                           uint8_t *out_inf);
+int ecgpu_batch_mul_ct_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, void *d_out_xy,
+                               void *d_out_inf);
+int ecgpu_lincomb_ct_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const uint8_t *points_xyz, size_t n, uint8_t *out_xy,
+                         uint8_t *out_inf);
+int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, void *d_out_xy,
+                             void *d_out_inf);
 
 /* Compressed points INTO the path (callers hold 33-byte SEC1 keys).  Like ecgpu_msm / ecgpu_batch_mul with
  * point i given as points_x[i] (L bytes, the curve's wire order) + points_tag[i]: 0x02 / 0x03 = the point with that x and even /
