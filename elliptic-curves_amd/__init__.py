@@ -63,6 +63,8 @@ ABI_SYMBOLS = [
     "ecgpu_batch_mul_compressed", "ecgpu_batch_mul_compressed_dev", "ecgpu_wipe", "ecgpu_group_exchange_reason",
     "ecgpu_set_table_policy", "ecgpu_set_table_budget", "ecgpu_base_table_info", "ecgpu_group_set_exchange_timeout", "ecgpu_group_set_exchange", "ecgpu_msm_parts_join_dev",
     "ecgpu_batch_mul_ct_xyz", "ecgpu_batch_mul_ct_xyz_dev", "ecgpu_lincomb_ct_xyz", "ecgpu_lincomb_ct_xyz_dev",
+    "ecgpu_batch_mul_xyz", "ecgpu_batch_mul_xyz_dev", "ecgpu_msm_xyz", "ecgpu_msm_xyz_dev", "ecgpu_batch_mul_base_and_mul_add_xyz",
+    "ecgpu_batch_mul_base_and_mul_add_xyz_dev", "ecgpu_msm_parts_xyz_dev", "ecgpu_group_msm_xyz", "ecgpu_group_msm_xyz_dev",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -166,8 +168,10 @@ def _need(what, a, nbytes):
 
 def _need_ct_xyz(constant_time):
     if not constant_time:
-        raise EcgpuError(ERR_ARG, "projective (X || Y || Z) records are taken by the uniform-schedule entry points only "
-                                  "(constant_time=True); for the variable-time ones normalise first (batch_normalize)")
+        raise EcgpuError(ERR_ARG, "mul_xyz / mul_xyz_dev are the uniform-schedule entry points (constant_time=True); the "
+                                  "variable-time forms for projective (X || Y || Z) records are Engine.mul_vartime_xyz[_dev], "
+                                  "Engine.lincomb_xyz[_dev], Engine.mul_by_generator_and_mul_add_xyz[_dev], "
+                                  "Engine.msm_parts_xyz_dev and Group.lincomb_xyz[_dev]")
 
 
 def _dp(t):
@@ -395,8 +399,8 @@ class Engine:
     def mul_xyz(self, curve, scalars, points_xyz, *, constant_time):
         """k_i * P_i for projective points P_i = X_i || Y_i || Z_i (3L bytes each, Z = 0 the identity), with no `to_affine` in
         front.  constant_time=True: the uniform-schedule entry point ecgpu_batch_mul_ct_xyz (`Mul<Scalar>` on a
-        `ProjectivePoint`).  The library has no variable-time entry point for projective records: constant_time=False raises
-        (normalise with batch_normalize and call `mul`), and the argument has no default until it has one."""
+        `ProjectivePoint`).  constant_time=False raises: the variable-time form is `mul_vartime_xyz` (the argument has no default,
+        so that no caller reaches the variable-time kernel by leaving it out)."""
         _need_ct_xyz(constant_time)
         L = _field_bytes(curve)
         s, p = _host(scalars), _host(points_xyz)
@@ -417,6 +421,42 @@ class Engine:
         inf = np.zeros(1, np.uint8)
         self._chk(self._lib.ecgpu_lincomb_ct_xyz(self._ctx, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
         return out, int(inf[0])
+
+    # the variable-time forms with projective points (X || Y || Z records, 3L bytes, Z = 0 the identity; no `to_affine` in front):
+    # the results and return codes of batch_normalize followed by `mul` / `lincomb` / `mul_by_generator_and_mul_add`
+    def mul_vartime_xyz(self, curve, scalars, points_xyz):
+        """k_i * P_i by ecgpu_batch_mul_xyz (`mul_vartime` on a `ProjectivePoint`)."""
+        L = _field_bytes(curve)
+        s, p = _host(scalars), _host(points_xyz)
+        n = s.size // L
+        _need("scalars", s, n * L); _need("points_xyz", p, n * 3 * L)
+        out = np.zeros(n * 2 * L, np.uint8)
+        inf = np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_batch_mul_xyz(self._ctx, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
+        return out, inf
+
+    def lincomb_xyz(self, curve, scalars, points_xyz):
+        """sum_i k_i P_i by ecgpu_msm_xyz (`lincomb_vartime` over `ProjectivePoint`s)."""
+        L = _field_bytes(curve)
+        s, p = _host(scalars), _host(points_xyz)
+        n = s.size // L
+        _need("scalars", s, n * L); _need("points_xyz", p, n * 3 * L)
+        out = np.zeros(2 * L, np.uint8)
+        inf = np.zeros(1, np.uint8)
+        self._chk(self._lib.ecgpu_msm_xyz(self._ctx, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
+        return out, int(inf[0])
+
+    def mul_by_generator_and_mul_add_xyz(self, curve, a_scalars, b_scalars, points_xyz):
+        """a_i G + b_i P_i by ecgpu_batch_mul_base_and_mul_add_xyz (`mul_by_generator_and_mul_add_vartime`)."""
+        L = _field_bytes(curve)
+        a, b, p = _host(a_scalars), _host(b_scalars), _host(points_xyz)
+        n = a.size // L
+        _need("a_scalars", a, n * L); _need("b_scalars", b, n * L); _need("points_xyz", p, n * 3 * L)
+        out = np.zeros(n * 2 * L, np.uint8)
+        inf = np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_batch_mul_base_and_mul_add_xyz(self._ctx, curve, _hp(a), _hp(b), _hp(p), ctypes.c_size_t(n),
+                                                                 _hp(out), _hp(inf)))
+        return out, inf
 
     def lincomb_compressed(self, curve, scalars, points_x, points_tag):
         """sum_i k_i P_i with SEC1-compressed points: points_x n*L bytes, points_tag n bytes (0x02 / 0x03, 0x00 = identity)."""
@@ -663,6 +703,18 @@ class Engine:
         self._chk(self._lib.ecgpu_lincomb_ct_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
                                                      _dp(d_out_xy), _dp(d_out_inf)))
 
+    def mul_vartime_xyz_dev(self, curve, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf=None):
+        self._chk(self._lib.ecgpu_batch_mul_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
+                                                    _dp(d_out_xy), _dp(d_out_inf)))
+
+    def lincomb_xyz_dev(self, curve, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf):
+        self._chk(self._lib.ecgpu_msm_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
+                                              _dp(d_out_xy), _dp(d_out_inf)))
+
+    def mul_by_generator_and_mul_add_xyz_dev(self, curve, d_a, d_b, d_points_xyz, n, d_out_xy, d_out_inf=None):
+        self._chk(self._lib.ecgpu_batch_mul_base_and_mul_add_xyz_dev(self._ctx, curve, _dp(d_a), _dp(d_b), _dp(d_points_xyz),
+                                                                     ctypes.c_size_t(n), _dp(d_out_xy), _dp(d_out_inf)))
+
     def lincomb_compressed_dev(self, curve, d_scalars, d_points_x, d_points_tag, n, d_out_xy, d_out_inf):
         self._chk(self._lib.ecgpu_msm_compressed_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_x), _dp(d_points_tag),
                                                      ctypes.c_size_t(n), _dp(d_out_xy), _dp(d_out_inf)))
@@ -682,6 +734,11 @@ class Engine:
     def msm_parts_dev(self, curve, d_scalars, d_points_xy, d_points_inf, n, plan_terms, d_parts):
         self._chk(self._lib.ecgpu_msm_parts_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xy), _dp(d_points_inf),
                                                 ctypes.c_size_t(n), ctypes.c_size_t(plan_terms), _dp(d_parts)))
+
+    def msm_parts_xyz_dev(self, curve, d_scalars, d_points_xyz, n, plan_terms, d_parts):
+        """msm_parts_dev over projective X || Y || Z records (ecgpu_msm_parts_xyz_dev)."""
+        self._chk(self._lib.ecgpu_msm_parts_xyz_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xyz), ctypes.c_size_t(n),
+                                                    ctypes.c_size_t(plan_terms), _dp(d_parts)))
 
     def msm_parts_join_dev(self, d_parts):
         """The context's stream waits (on the device) for the local half that wrote `d_parts` on a lane (include/ecgpu.h)."""
@@ -801,6 +858,31 @@ class Group:
         out = np.zeros(2 * L, np.uint8)
         inf = np.zeros(1, np.uint8)
         self._chk(self._lib.ecgpu_group_msm_dev(self._g, curve, ds, dp, di, cnt, _hp(out), _hp(inf)))
+        return out, int(inf[0])
+
+    def lincomb_xyz(self, curve, scalars, points_xyz):
+        """`lincomb` over projective X || Y || Z records (ecgpu_group_msm_xyz)."""
+        L = _field_bytes(curve)
+        s, p = _host(scalars), _host(points_xyz)
+        n = s.size // L
+        if p.size != n * 3 * L:
+            raise EcgpuError(ERR_ARG, "lincomb_xyz: buffer sizes do not match %d terms" % n)
+        out = np.zeros(2 * L, np.uint8)
+        inf = np.zeros(1, np.uint8)
+        self._chk(self._lib.ecgpu_group_msm_xyz(self._g, curve, _hp(s), _hp(p), ctypes.c_size_t(n), _hp(out), _hp(inf)))
+        return out, int(inf[0])
+
+    def lincomb_xyz_dev(self, curve, d_scalars, d_points_xyz, n_per_device):
+        """`lincomb_dev` over projective X || Y || Z records (ecgpu_group_msm_xyz_dev)."""
+        L = _field_bytes(curve)
+        m = self.size
+        if not (len(d_scalars) == len(d_points_xyz) == len(n_per_device) == m):
+            raise EcgpuError(ERR_ARG, "lincomb_xyz_dev: one entry per group member expected")
+        arr = lambda xs: (ctypes.c_void_p * m)(*[(_dp(x).value if x is not None else None) for x in xs])
+        cnt = (ctypes.c_size_t * m)(*[int(v) for v in n_per_device])
+        out = np.zeros(2 * L, np.uint8)
+        inf = np.zeros(1, np.uint8)
+        self._chk(self._lib.ecgpu_group_msm_xyz_dev(self._g, curve, arr(d_scalars), arr(d_points_xyz), cnt, _hp(out), _hp(inf)))
         return out, int(inf[0])
 
     def mul_by_generator(self, curve, scalars):

@@ -103,6 +103,7 @@ struct ecgpu_ctx {
     DevBuf ec_winv;                    // the batch's s^-1 / r^-1 modulo the group order (k_scalar_batch_inv; its prefix products use `prefix`)
     DevBuf ct_flags;             // one verdict byte per element of a uniform-schedule batch
     DevBuf cx_xy, cx_inf;        // x || y + flag records decoded from compressed input (ecgpu_msm_compressed, ecgpu_batch_mul_compressed)
+                                 // or converted from projective input (the variable-time _xyz forms; their product chain uses `prefix`)
     bool keep_status = false;    // the status word already holds the verdicts of a first stage of the call: do not clear it
     hipEvent_t ev[9] = {};       // 0..2 call spans, 3..4 the MSM's sort / accumulate marks, 5 spare, 6..8 MsmPlan::detail
     std::map<std::string, double> timing;
@@ -118,6 +119,7 @@ struct ecgpu_ctx {
     struct MsmLane {
         hipStream_t s = nullptr;
         DevBuf ws, proj, prefix;
+        DevBuf cx_xy, cx_inf;              // x || y + flag records converted from X || Y || Z input on this lane (ecgpu_msm_xyz_dev)
         hipEvent_t ev_in = nullptr, ev_a = nullptr, ev_b = nullptr, ev_done = nullptr;
         const void* parts_out = nullptr;   // the parts record an ecgpu_msm_parts_dev on this lane wrote last (ecgpu_msm_parts_join_dev)
     };
@@ -726,6 +728,34 @@ int point_sum_dev(ecgpu_ctx* ctx, const void* d_xy, const void* d_inf, size_t n,
     return rc;
 }
 
+// ---- projective points into the variable-time path: X || Y || Z records are normalised on the device (k_xyz_affine: one
+// inversion per lane of records, the verdicts of the _ct_xyz forms) into x || y + identity flag records on stream s, in the
+// buffers given (the context's own, or an MSM lane's); the affine pipeline then runs unchanged on them.  A bad record sets
+// ST_BAD_POINT like an off-curve x || y record would.
+template <class C>
+int xyz_stage(ecgpu_ctx* ctx, hipStream_t s, const void* d_xyz, size_t n, DevBuf& xy, DevBuf& inf, DevBuf& prefix) {
+    constexpr int WB = WireBytes<C>::value, NS = Field<C>::NS;
+    int rc;
+    if ((rc = ensure_on(ctx, s, xy, n * 2 * WB + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure_on(ctx, s, inf, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure_on(ctx, s, prefix, n * NS * 4 + 16)) != ECGPU_OK) return rc;
+    launch_xyz_affine<C>(s, (const uint8_t*)d_xyz, n, (uint32_t*)prefix.p, (uint8_t*)xy.p, (uint8_t*)inf.p, ctx->d_status);
+    return ECGPU_OK;
+}
+// the same as the first stage of a call on the context's stream (the pattern of decode_compressed: the second stage runs under
+// KeepStatus)
+template <class C>
+int decode_xyz(ecgpu_ctx* ctx, const void* d_xyz, size_t n) {
+    int rc;
+    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    return xyz_stage<C>(ctx, ctx->stream, d_xyz, n, ctx->cx_xy, ctx->cx_inf, ctx->prefix);
+}
+struct KeepStatus {            // the second stage of a two-stage call must not clear the first stage's verdicts
+    ecgpu_ctx* ctx;
+    explicit KeepStatus(ecgpu_ctx* c) : ctx(c) { ctx->keep_status = true; }
+    ~KeepStatus() { ctx->keep_status = false; }
+};
+
 // The lane the next MSM (or local half of a sharded MSM) of an asynchronous context with ecgpu_set_msm_lanes > 1 goes to: lanes take
 // turns; a lane's stream, events and workspace exist from its first use on.
 int next_lane(ecgpu_ctx* ctx, size_t workspace_bytes, ecgpu_ctx::MsmLane** out) {
@@ -757,9 +787,11 @@ size_t msm_small_max() {
     return lg <= 0 ? 0 : (size_t)1 << (lg > 24 ? 24 : lg);
 }
 
+// xyz: d_xy holds projective records X || Y || Z and d_inf is unused — converted on the MSM's lane when it goes to one, on the
+// context's stream otherwise
 template <class C>
 int msm_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy,
-            void* d_out_inf) {
+            void* d_out_inf, bool xyz = false) {
     constexpr int N = C::N, NS = Field<C>::NS;
     (void)N;
     int rc;
@@ -767,7 +799,13 @@ int msm_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void*
         ctx->err = "MSM of 2^31 (k256: 2^30) or more terms: split it and add the partial sums (ecgpu_point_sum)";
         return ECGPU_ERR_ARG;
     }
-    if (n >= 1 && n <= msm_small_max<C>() && ctx->msm_c == 0) {
+    const bool small = n >= 1 && n <= msm_small_max<C>() && ctx->msm_c == 0;
+    if (xyz && (small || !(ctx->async && ctx->msm_lanes > 1))) {
+        if ((rc = decode_xyz<C>(ctx, d_xy, n)) != ECGPU_OK) return rc;
+        KeepStatus keep(ctx);
+        return msm_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+    }
+    if (small) {
         // Small MSM: the bucket method has a floor of ~1.2 ms of serial work that does not depend on n (running sums, the
         // 240-doubling combine chain).  Below ~2^17 terms one variable-base multiplication per term (all lanes in
         // parallel, ~0.5 ms of latency) and a tree sum of the products are faster.
@@ -802,6 +840,11 @@ int msm_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void*
         if ((rc = ensure_on(ctx, l.s, l.prefix, NS * 4)) != ECGPU_OK) return rc;
         HIP_TRY(ctx, hipEventRecord(l.ev_in, ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(l.s, l.ev_in, 0));
+        if (xyz) {        // the conversion too: on the lane, into the lane's buffers, beside the previous MSM
+            if ((rc = xyz_stage<C>(ctx, l.s, d_xy, n, l.cx_xy, l.cx_inf, l.prefix)) != ECGPU_OK) return rc;
+            d_xy = l.cx_xy.p;
+            d_inf = l.cx_inf.p;
+        }
         launch_msm<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, l.ws.p, (uint32_t*)l.proj.p,
                       ctx->d_status, l.ev_a, l.ev_b, (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);   // (the last kernel writes the wire record)
         // Any OTHER entry point called later on this context waits for this event first (reset_status): it may read the
@@ -889,11 +932,6 @@ int decode_compressed(ecgpu_ctx* ctx, const void* d_x, const void* d_tag, size_t
                                     (uint8_t*)ctx->cx_inf.p, ctx->d_status);
     return ECGPU_OK;
 }
-struct KeepStatus {            // the second stage of a two-stage call must not clear the first stage's verdicts
-    ecgpu_ctx* ctx;
-    explicit KeepStatus(ecgpu_ctx* c) : ctx(c) { ctx->keep_status = true; }
-    ~KeepStatus() { ctx->keep_status = false; }
-};
 template <class C>
 int msm_compressed_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_x, const void* d_tag, size_t n, void* d_out_xy,
                        void* d_out_inf) {
@@ -910,11 +948,55 @@ int mul_var_compressed_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_
     KeepStatus keep(ctx);
     return mul_var_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
 }
+template <class C>
+int mul_var_xyz_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xyz, size_t n, void* d_out_xy, void* d_out_inf) {
+    int rc;
+    if (n == 0) return ECGPU_OK;
+    if ((rc = decode_xyz<C>(ctx, d_xyz, n)) != ECGPU_OK) return rc;
+    KeepStatus keep(ctx);
+    return mul_var_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+}
+
+// aG + bP per element = two-term lincomb (mul_backend.rs:29-40).  Evaluated as a*G (table kernel) and b*P (variable-base
+// kernel) into projective scratch halves, then one complete addition per element.
+template <class C>
+int mul_add_dev(ecgpu_ctx* ctx, const void* d_a, const void* d_b, const void* d_points_xy, const void* d_points_inf, size_t n,
+                void* d_out_xy, void* d_out_inf) {
+    constexpr int NS = Field<C>::NS;
+    int rc;
+    if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
+    if (n == 0) return (int)ECGPU_OK;
+    size_t tstride = var_base_slots<C>(n);
+    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
+    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    const Table& t = ctx->table[C::ID];
+    uint32_t* pa = (uint32_t*)ctx->proj.p;
+    record(ctx, 0);
+    launch_fixed_base<C>(ctx->stream, (const uint8_t*)d_a, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
+    launch_var_base<C>(ctx->stream, (const uint8_t*)d_b, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
+                       (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);                                   // pa[i] += b[i] P[i]
+    record(ctx, 1);
+    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
+    record(ctx, 2);
+    rc = finish(ctx);
+    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
+    return rc;
+}
+template <class C>
+int mul_add_xyz_dev(ecgpu_ctx* ctx, const void* d_a, const void* d_b, const void* d_xyz, size_t n, void* d_out_xy, void* d_out_inf) {
+    int rc;
+    if (n == 0) return mul_add_dev<C>(ctx, d_a, d_b, nullptr, nullptr, 0, d_out_xy, d_out_inf);
+    if ((rc = decode_xyz<C>(ctx, d_xyz, n)) != ECGPU_OK) return rc;
+    KeepStatus keep(ctx);
+    return mul_add_dev<C>(ctx, d_a, d_b, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+}
 
 // ---- an MSM whose terms are spread over several GPUs: local half / combining half ------------------------
+// xyz: d_xy holds projective records X || Y || Z and d_inf is unused (converted as in msm_dev)
 template <class C>
 int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, size_t plan_terms,
-                  void* d_parts) {
+                  void* d_parts, bool xyz = false) {
     int rc;
     if (n > msm_max_terms<C>() || plan_terms > msm_max_terms<C>()) {
         ctx->err = "MSM shard of 2^31 (k256: 2^30) or more terms";
@@ -923,6 +1005,11 @@ int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const
     if (plan_terms < n) {
         ctx->err = "ecgpu_msm_parts_dev: plan_terms must be at least the shard's term count (and the same on every GPU)";
         return ECGPU_ERR_ARG;
+    }
+    if (xyz && !(ctx->async && ctx->msm_lanes > 1)) {
+        if ((rc = decode_xyz<C>(ctx, d_xy, n)) != ECGPU_OK) return rc;
+        KeepStatus keep(ctx);
+        return msm_parts_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, plan_terms, d_parts);
     }
     const int c = ctx->msm_c ? ctx->msm_c : msm_choose_window<C>(plan_terms);
     MsmPlan plan = msm_plan<C>(n, c, msm_use_glv<C>(plan_terms));
@@ -942,6 +1029,11 @@ int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const
         if (l.parts_out) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.ev_done, 0));
         HIP_TRY(ctx, hipEventRecord(l.ev_in, ctx->stream));
         HIP_TRY(ctx, hipStreamWaitEvent(l.s, l.ev_in, 0));
+        if (xyz) {        // the conversion on the lane, into the lane's buffers
+            if ((rc = xyz_stage<C>(ctx, l.s, d_xy, n, l.cx_xy, l.cx_inf, l.prefix)) != ECGPU_OK) return rc;
+            d_xy = l.cx_xy.p;
+            d_inf = l.cx_inf.p;
+        }
         launch_msm_parts<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, l.ws.p, (uint32_t*)d_parts,
                             ctx->d_status, l.ev_a, l.ev_b);
         HIP_TRY(ctx, hipEventRecord(l.ev_done, l.s));
@@ -1310,7 +1402,7 @@ void ecgpu_destroy(ecgpu_ctx* ctx) {
         if (b->p) (void)hipFree(b->p);
     for (auto& l : ctx->lane) {
         if (l.s) (void)hipStreamSynchronize(l.s);
-        for (DevBuf* b : {&l.ws, &l.proj, &l.prefix})
+        for (DevBuf* b : {&l.ws, &l.proj, &l.prefix, &l.cx_xy, &l.cx_inf})
             if (b->p) (void)hipFree(b->p);
         for (hipEvent_t e : {l.ev_in, l.ev_a, l.ev_b, l.ev_done})
             if (e) (void)hipEventDestroy(e);
@@ -1506,7 +1598,7 @@ int ecgpu_wipe(ecgpu_ctx* ctx) {
                       &ctx->ec_s, &ctx->ec_id, &ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf})
         if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     for (auto& l : ctx->lane)
-        for (DevBuf* b : {&l.ws, &l.proj, &l.prefix})
+        for (DevBuf* b : {&l.ws, &l.proj, &l.prefix, &l.cx_xy, &l.cx_inf})
             if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ECGPU_OK;
@@ -1628,6 +1720,24 @@ int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, c
     });
 }
 
+int ecgpu_batch_mul_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
+                            void* d_out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (n && (!d_scalars || !d_points_xyz || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xyz) || !aligned16(d_out_xy)))
+        return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) { return mul_var_xyz_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf); });
+}
+
+int ecgpu_msm_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
+                      void* d_out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
+    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) {
+        return msm_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
+    });
+}
+
 int ecgpu_msm_compressed_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_x, const void* d_points_tag,
                              size_t n, void* d_out_xy, void* d_out_inf) {
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
@@ -1680,6 +1790,16 @@ int ecgpu_msm_parts_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const 
     });
 }
 
+int ecgpu_msm_parts_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, size_t plan_terms,
+                            void* d_parts) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (!d_parts || !aligned16(d_parts)) return arg_error(ctx, __func__);
+    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) {
+        return msm_parts_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, plan_terms, d_parts, true);
+    });
+}
+
 int ecgpu_msm_parts_join_dev(ecgpu_ctx* ctx, const void* d_parts) {
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
     if (!d_parts) return arg_error(ctx, __func__);
@@ -1720,35 +1840,24 @@ int ecgpu_point_sum_dev(ecgpu_ctx* ctx, int curve, const void* d_points_xy, cons
 int ecgpu_batch_mul_base_and_mul_add_dev(ecgpu_ctx* ctx, int curve, const void* d_a, const void* d_b,
                                          const void* d_points_xy, const void* d_points_inf, size_t n, void* d_out_xy,
                                          void* d_out_inf) {
-    // aG + bP per element = two-term lincomb (mul_backend.rs:29-40).  Evaluated as a*G (table kernel) and
-    // b*P (variable-base kernel) into projective scratch halves, then one complete addition per element.
+    // (mul_add_dev)
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
     if (n && (!d_a || !d_b || !d_points_xy || !d_out_xy || !aligned16(d_a) || !aligned16(d_b) ||
               !aligned16(d_points_xy) || !aligned16(d_out_xy)))
         return arg_error(ctx, __func__);
     return dispatch(curve, [&](auto c) {
-        using C = decltype(c);
-        constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
-        int rc;
-        if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
-        if (n == 0) return (int)ECGPU_OK;
-        size_t tstride = var_base_slots<C>(n);
-        if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-        if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-        const Table& t = ctx->table[C::ID];
-        uint32_t* pa = (uint32_t*)ctx->proj.p;
-            record(ctx, 0);
-        launch_fixed_base<C>(ctx->stream, (const uint8_t*)d_a, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
-        launch_var_base<C>(ctx->stream, (const uint8_t*)d_b, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
-                           (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);                                   // pa[i] += b[i] P[i]
-        record(ctx, 1);
-        if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-        record(ctx, 2);
-        rc = finish(ctx);
-        collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-        return rc;
+        return mul_add_dev<decltype(c)>(ctx, d_a, d_b, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
+    });
+}
+
+int ecgpu_batch_mul_base_and_mul_add_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_a, const void* d_b, const void* d_points_xyz,
+                                             size_t n, void* d_out_xy, void* d_out_inf) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (n && (!d_a || !d_b || !d_points_xyz || !d_out_xy || !aligned16(d_a) || !aligned16(d_b) || !aligned16(d_points_xyz) ||
+              !aligned16(d_out_xy)))
+        return arg_error(ctx, __func__);
+    return dispatch(curve, [&](auto c) {
+        return mul_add_xyz_dev<decltype(c)>(ctx, d_a, d_b, d_points_xyz, n, d_out_xy, d_out_inf);
     });
 }
 
@@ -1978,11 +2087,11 @@ int ecgpu_batch_mul_base_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* sc
 }
 
 // the host-pointer batch multiplication over either point record: affine x || y (+ optional identity flags) for
-// ecgpu_batch_mul[_ct], projective X || Y || Z (3L bytes, no flags) for ecgpu_batch_mul_ct_xyz
+// ecgpu_batch_mul[_ct], projective X || Y || Z (3L bytes, no flags) for ecgpu_batch_mul[_ct]_xyz
 static int batch_mul_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points, const uint8_t* points_inf,
                           size_t n, uint8_t* out_xy, uint8_t* out_inf, bool ct, bool xyz, const char* fn) {
     const auto dev = [&](const void* k, const void* p, const void* pi, size_t m, void* o, void* oi) {
-        if (xyz) return ecgpu_batch_mul_ct_xyz_dev(ctx, curve, k, p, m, o, oi);
+        if (xyz) return ct ? ecgpu_batch_mul_ct_xyz_dev(ctx, curve, k, p, m, o, oi) : ecgpu_batch_mul_xyz_dev(ctx, curve, k, p, m, o, oi);
         return ct ? ecgpu_batch_mul_ct_dev(ctx, curve, k, p, pi, m, o, oi) : ecgpu_batch_mul_dev(ctx, curve, k, p, pi, m, o, oi);
     };
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
@@ -2024,15 +2133,22 @@ int ecgpu_batch_mul_ct_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, co
                            uint8_t* out_inf) {
     return batch_mul_host(ctx, curve, scalars, points_xyz, nullptr, n, out_xy, out_inf, true, true, __func__);
 }
+int ecgpu_batch_mul_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
+                        uint8_t* out_inf) {
+    return batch_mul_host(ctx, curve, scalars, points_xyz, nullptr, n, out_xy, out_inf, false, true, __func__);
+}
 
-int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
-              size_t n, uint8_t* out_xy, uint8_t* out_inf) {
+// the host-pointer MSM over either point record: affine x || y (+ optional identity flags) for ecgpu_msm, projective
+// X || Y || Z (3L bytes, no flags) for ecgpu_msm_xyz
+static int msm_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
+                    size_t n, uint8_t* out_xy, uint8_t* out_inf, bool xyz, const char* fn) {
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
     SyncScope sync_scope(ctx);
     if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
     size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (!out_xy || (n && (!scalars || !points_xy))) return arg_error(ctx, __func__);
+    if (!L) return curve_error(ctx, fn);
+    if (!out_xy || (n && (!scalars || !points_xy))) return arg_error(ctx, fn);
+    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
     int rc;
     const size_t pipe_chunk = msm_pipe_chunk();
     if (n >= 2 * pipe_chunk) {
@@ -2048,11 +2164,12 @@ int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* 
         uint8_t* part_inf = (uint8_t*)ctx->out1.p + 16;
         return dispatch(curve, [&](auto c) -> int {
             using C = decltype(c);
-            int r = pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_xy, &ctx->in1, 2 * L}, {points_inf, &ctx->in2, 1}}, {},
+            int r = pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}}, {},
                               [&](size_t off, size_t m) {
                                   const size_t j = off / pipe_chunk;
-                                  return msm_dev<C>(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L,
-                                                    points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, part_xy + j * 2 * L, part_inf + j);
+                                  return msm_dev<C>(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
+                                                    points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, part_xy + j * 2 * L, part_inf + j,
+                                                    xyz);
                               },
                               pipe_chunk);
             if (r != ECGPU_OK) return r;
@@ -2062,15 +2179,25 @@ int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* 
         });
     }
     if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
+    if ((rc = upload(ctx, ctx->in1, points_xy, n * PB)) != ECGPU_OK) return rc;
     if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_msm_dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
-                            ctx->out1.p)) != ECGPU_OK)
+    if ((rc = xyz ? ecgpu_msm_xyz_dev(ctx, curve, ctx->in0.p, ctx->in1.p, n, ctx->out0.p, ctx->out1.p)
+                  : ecgpu_msm_dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
+                                  ctx->out1.p)) != ECGPU_OK)
         return rc;
     if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
     return download(ctx, out_inf, ctx->out1, 1);
+}
+
+int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
+              size_t n, uint8_t* out_xy, uint8_t* out_inf) {
+    return msm_host(ctx, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, false, __func__);
+}
+int ecgpu_msm_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
+                  uint8_t* out_inf) {
+    return msm_host(ctx, curve, scalars, points_xyz, nullptr, n, out_xy, out_inf, true, __func__);
 }
 
 int ecgpu_lincomb_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
@@ -2183,35 +2310,49 @@ int ecgpu_batch_mul_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* scalars
     return download(ctx, out_inf, ctx->out1, n);
 }
 
-int ecgpu_batch_mul_base_and_mul_add(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars,
-                                     const uint8_t* points_xy, const uint8_t* points_inf, size_t n, uint8_t* out_xy,
-                                     uint8_t* out_inf) {
+// the host-pointer aG + bP batch over either point record: affine x || y (+ optional identity flags) for
+// ecgpu_batch_mul_base_and_mul_add, projective X || Y || Z (3L bytes, no flags) for its _xyz form
+static int mul_add_host(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars, const uint8_t* points_xy,
+                        const uint8_t* points_inf, size_t n, uint8_t* out_xy, uint8_t* out_inf, bool xyz, const char* fn) {
+    const auto dev = [&](const void* a, const void* b, const void* p, const void* pi, size_t m, void* o, void* oi) {
+        if (xyz) return ecgpu_batch_mul_base_and_mul_add_xyz_dev(ctx, curve, a, b, p, m, o, oi);
+        return ecgpu_batch_mul_base_and_mul_add_dev(ctx, curve, a, b, p, pi, m, o, oi);
+    };
     if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
     SyncScope sync_scope(ctx);
     if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
     size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!a_scalars || !b_scalars || !points_xy || !out_xy)) return arg_error(ctx, __func__);
+    if (!L) return curve_error(ctx, fn);
+    if (n && (!a_scalars || !b_scalars || !points_xy || !out_xy)) return arg_error(ctx, fn);
+    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
     int rc;
     if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{a_scalars, &ctx->in0, L}, {b_scalars, &ctx->in3, L}, {points_xy, &ctx->in1, 2 * L}, {points_inf, &ctx->in2, 1}},
+        return pipelined(ctx, n, {{a_scalars, &ctx->in0, L}, {b_scalars, &ctx->in3, L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
                          {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_batch_mul_base_and_mul_add_dev(
-                                 ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L,
-                                 points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
+                             return dev((uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
+                                        points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, (uint8_t*)ctx->out0.p + off * 2 * L,
+                                        (uint8_t*)ctx->out1.p + off);
                          });
     if ((rc = upload(ctx, ctx->in0, a_scalars, n * L)) != ECGPU_OK) return rc;
     if ((rc = upload(ctx, ctx->in3, b_scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
+    if ((rc = upload(ctx, ctx->in1, points_xy, n * PB)) != ECGPU_OK) return rc;
     if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_batch_mul_base_and_mul_add_dev(ctx, curve, ctx->in0.p, ctx->in3.p, ctx->in1.p,
-                                                   points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p, ctx->out1.p)) !=
-        ECGPU_OK)
+    if ((rc = dev(ctx->in0.p, ctx->in3.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK)
         return rc;
     if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
     return download(ctx, out_inf, ctx->out1, n);
+}
+
+int ecgpu_batch_mul_base_and_mul_add(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars,
+                                     const uint8_t* points_xy, const uint8_t* points_inf, size_t n, uint8_t* out_xy,
+                                     uint8_t* out_inf) {
+    return mul_add_host(ctx, curve, a_scalars, b_scalars, points_xy, points_inf, n, out_xy, out_inf, false, __func__);
+}
+int ecgpu_batch_mul_base_and_mul_add_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars,
+                                         const uint8_t* points_xyz, size_t n, uint8_t* out_xy, uint8_t* out_inf) {
+    return mul_add_host(ctx, curve, a_scalars, b_scalars, points_xyz, nullptr, n, out_xy, out_inf, true, __func__);
 }
 
 int ecgpu_ecdsa_verify_batch(ecgpu_ctx* ctx, int curve, const uint8_t* z, const uint8_t* r, const uint8_t* s,

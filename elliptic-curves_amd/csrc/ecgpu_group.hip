@@ -353,8 +353,9 @@ int ecgpu_group_set_msm_window(ecgpu_group* g, int window_bits) {
     return ECGPU_OK;
 }
 
-int ecgpu_group_msm_dev(ecgpu_group* g, int curve, const void* const* d_scalars, const void* const* d_points_xy,
-                        const void* const* d_points_inf, const size_t* n_per_device, uint8_t* out_xy, uint8_t* out_inf) {
+// xyz: d_points_xy[i] hold projective records X || Y || Z (ecgpu_msm_parts_xyz_dev) and d_points_inf is unused
+static int group_msm_dev(ecgpu_group* g, int curve, const void* const* d_scalars, const void* const* d_points_xy,
+                         const void* const* d_points_inf, const size_t* n_per_device, uint8_t* out_xy, uint8_t* out_inf, bool xyz) {
     if (!g) return ECGPU_ERR_ARG;
     g->err.clear();
     const size_t L = ecgpu_field_bytes(curve);
@@ -440,8 +441,9 @@ int ecgpu_group_msm_dev(ecgpu_group* g, int curve, const void* const* d_scalars,
             if (with_parts) {
                 if ((e = ecgpu_set_async(mb.ctx, 1)) != ECGPU_OK) return bail(e);
                 scope.ctx = mb.ctx;
-                e = ecgpu_msm_parts_dev(mb.ctx, curve, d_scalars[r], d_points_xy[r], d_points_inf ? d_points_inf[r] : nullptr, n_per_device[r],
-                                        plan_terms, mb.d_parts);
+                e = xyz ? ecgpu_msm_parts_xyz_dev(mb.ctx, curve, d_scalars[r], d_points_xy[r], n_per_device[r], plan_terms, mb.d_parts)
+                        : ecgpu_msm_parts_dev(mb.ctx, curve, d_scalars[r], d_points_xy[r], d_points_inf ? d_points_inf[r] : nullptr,
+                                              n_per_device[r], plan_terms, mb.d_parts);
                 if (e == ECGPU_OK && hipEventRecord(mb.ev_parts, mb.work) != hipSuccess) e = ECGPU_ERR_HIP;
                 // the local half: compute, it ends; its input errors (a scalar >= n, a point off the curve) are the call's result
                 if (e == ECGPU_OK) e = hipEventSynchronize(mb.ev_parts) == hipSuccess ? ecgpu_synchronize(mb.ctx) : ECGPU_ERR_HIP;
@@ -576,13 +578,24 @@ int ecgpu_group_msm_dev(ecgpu_group* g, int curve, const void* const* d_scalars,
     return ECGPU_OK;
 }
 
-int ecgpu_group_msm(ecgpu_group* g, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
-                    size_t n, uint8_t* out_xy, uint8_t* out_inf) {
+int ecgpu_group_msm_dev(ecgpu_group* g, int curve, const void* const* d_scalars, const void* const* d_points_xy,
+                        const void* const* d_points_inf, const size_t* n_per_device, uint8_t* out_xy, uint8_t* out_inf) {
+    return group_msm_dev(g, curve, d_scalars, d_points_xy, d_points_inf, n_per_device, out_xy, out_inf, false);
+}
+int ecgpu_group_msm_xyz_dev(ecgpu_group* g, int curve, const void* const* d_scalars, const void* const* d_points_xyz,
+                            const size_t* n_per_device, uint8_t* out_xy, uint8_t* out_inf) {
+    return group_msm_dev(g, curve, d_scalars, d_points_xyz, nullptr, n_per_device, out_xy, out_inf, true);
+}
+
+// the host-pointer form over either point record: affine x || y (+ optional flags), or X || Y || Z (3L bytes) for the _xyz form
+static int group_msm(ecgpu_group* g, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
+                     size_t n, uint8_t* out_xy, uint8_t* out_inf, bool xyz) {
     if (!g) return ECGPU_ERR_ARG;
     g->err.clear();
     const size_t L = ecgpu_field_bytes(curve);
     if (!L) return fail(g, ECGPU_ERR_CURVE, "unknown curve id");
     if (!out_xy || (n && (!scalars || !points_xy))) return fail(g, ECGPU_ERR_ARG, "ecgpu_group_msm: NULL argument");
+    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
     const int nd = (int)g->m.size();
     std::vector<const void*> ds(nd), dp(nd), di(nd);
     std::vector<size_t> cnt(nd);
@@ -595,9 +608,9 @@ int ecgpu_group_msm(ecgpu_group* g, int curve, const uint8_t* scalars, const uin
         cnt[r] = m;
         int e;
         if ((e = grow(g, mb, &mb.d_in0, &mb.in0_cap, m * L + 16)) != ECGPU_OK) return e;
-        if ((e = grow(g, mb, &mb.d_in1, &mb.in1_cap, m * 2 * L + 16)) != ECGPU_OK) return e;
+        if ((e = grow(g, mb, &mb.d_in1, &mb.in1_cap, m * PB + 16)) != ECGPU_OK) return e;
         if ((e = ecgpu_copy_to_device(mb.ctx, mb.d_in0, scalars + lo * L, m * L)) != ECGPU_OK) return e;
-        if ((e = ecgpu_copy_to_device(mb.ctx, mb.d_in1, points_xy + lo * 2 * L, m * 2 * L)) != ECGPU_OK) return e;
+        if ((e = ecgpu_copy_to_device(mb.ctx, mb.d_in1, points_xy + lo * PB, m * PB)) != ECGPU_OK) return e;
         ds[r] = mb.d_in0;
         dp[r] = mb.d_in1;
         di[r] = nullptr;
@@ -611,7 +624,15 @@ int ecgpu_group_msm(ecgpu_group* g, int curve, const uint8_t* scalars, const uin
         return ECGPU_OK;
     });
     if (rc != ECGPU_OK) return rc;
-    return ecgpu_group_msm_dev(g, curve, ds.data(), dp.data(), points_inf ? di.data() : nullptr, cnt.data(), out_xy, out_inf);
+    return group_msm_dev(g, curve, ds.data(), dp.data(), points_inf ? di.data() : nullptr, cnt.data(), out_xy, out_inf, xyz);
+}
+int ecgpu_group_msm(ecgpu_group* g, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
+                    size_t n, uint8_t* out_xy, uint8_t* out_inf) {
+    return group_msm(g, curve, scalars, points_xy, points_inf, n, out_xy, out_inf, false);
+}
+int ecgpu_group_msm_xyz(ecgpu_group* g, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
+                        uint8_t* out_inf) {
+    return group_msm(g, curve, scalars, points_xyz, nullptr, n, out_xy, out_inf, true);
 }
 
 int ecgpu_group_batch_mul_base(ecgpu_group* g, int curve, const uint8_t* scalars, size_t n, uint8_t* out_xy, uint8_t* out_inf) {

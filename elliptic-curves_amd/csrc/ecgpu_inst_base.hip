@@ -61,6 +61,16 @@ template <> void launch_fixed_base<CurveT>(hipStream_t s, const uint8_t* scalars
     else
         hipLaunchKernelGGL((k_fixed_base<CurveT, false>), dim3(grid_for(n)), dim3(BLOCK), 0, s, scalars, n, table, w, nwin, proj_out, status);
 }
+// the lanes of launch_normalize: K = ceil(n / 65536) records per lane, at most 64, one inversion each
+template <> void launch_xyz_affine<CurveT>(hipStream_t s, const uint8_t* xyz, size_t n, uint32_t* prefix, uint8_t* out_xy,
+                                           uint8_t* out_inf, int* status) {
+    if (n == 0) return;
+    size_t k = (n + 65535) / 65536;
+    if (k > 64) k = 64;
+    const size_t nthreads = (n + k - 1) / k;
+    hipLaunchKernelGGL(k_xyz_affine<CurveT>, dim3(grid_for(nthreads)), dim3(BLOCK), 0, s, xyz, prefix, n, nthreads, out_xy, out_inf,
+                       status);
+}
 template <> void launch_load_proj<CurveT>(hipStream_t s, const uint8_t* xyz, size_t n, uint32_t* proj_out, int* status) {
     hipLaunchKernelGGL(k_load_proj<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, xyz, n, proj_out, status);
 }

@@ -20,6 +20,7 @@
 #include "ecgpu_point.h"
 #include "ecgpu_recode.h"
 #include "ecgpu_fixedmul.h"
+#include "ecgpu_xyz.h"
 
 namespace ecgpu {
 
@@ -458,6 +459,46 @@ __global__ void __launch_bounds__(BLOCK) k_normalize(const uint32_t* proj, uint3
         }
         if (j < nthreads) break;
     }
+}
+
+// ---- projective records into the variable-time path: X || Y || Z -> x || y + identity flags ----------------------------
+// (ecgpu_msm_xyz, ecgpu_batch_mul_xyz, ecgpu_batch_mul_base_and_mul_add_xyz, ecgpu_msm_parts_xyz_dev: the affine pipelines run
+// unchanged behind it).  Lanes and the inversion per lane as in k_normalize, but the records are read from the caller's wire
+// array itself — Z in the product pass, X || Y || Z and the prefix in the back pass — and no projective copy is made: 290 bytes
+// of traffic per k256 record against ~590 for k_load_proj + k_normalize.  The lane body, its verdicts and its reference
+// citations are in ecgpu_xyz.h.
+template <class C>
+struct XyzIoHbm {
+    static constexpr int WB = WireBytes<C>::value, NS = Field<C>::NS;
+    const uint8_t* xyz;
+    uint32_t* prefix;
+    uint8_t* out_xy;
+    uint8_t* out_inf;
+    bool bad;
+    __device__ void load_z(size_t j, uint32_t* cz) const { load_wire<C>(cz, xyz + j * (3 * WB) + 2 * WB); }
+    __device__ void load_xyz(size_t j, uint32_t* cx, uint32_t* cy, uint32_t* cz) const {
+        load_wire<C>(cx, xyz + j * (3 * WB));
+        load_wire<C>(cy, xyz + j * (3 * WB) + WB);
+        load_wire<C>(cz, xyz + j * (3 * WB) + 2 * WB);
+    }
+    __device__ void put_prefix(size_t j, const uint32_t* w) const { store_words_vec<NS>(prefix + j * NS, w); }
+    __device__ void get_prefix(size_t j, uint32_t* w) const { load_words_vec<NS>(w, prefix + j * NS); }
+    __device__ void put_affine(size_t j, const uint32_t* x, const uint32_t* y, bool ident) const {
+        store_wire<C>(out_xy + j * (2 * WB), x);
+        store_wire<C>(out_xy + j * (2 * WB) + WB, y);
+        out_inf[j] = ident ? 1 : 0;
+    }
+    __device__ void verdict(size_t, bool ok) { bad = bad || !ok; }
+};
+template <class C>
+__global__ void __launch_bounds__(BLOCK) k_xyz_affine(const uint8_t* __restrict__ xyz, uint32_t* __restrict__ prefix, size_t n,
+                                                      size_t nthreads, uint8_t* __restrict__ out_xy, uint8_t* __restrict__ out_inf,
+                                                      int* status) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= nthreads) return;
+    XyzIoHbm<C> io{xyz, prefix, out_xy, out_inf, false};
+    xyz_affine_lane<C>(t, n, nthreads, io);
+    if (io.bad) atomicOr(status, ST_BAD_POINT);
 }
 
 // ---- fixed base: out[i] = k[i] * G -----------------------------------------------------------------

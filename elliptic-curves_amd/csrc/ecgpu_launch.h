@@ -53,6 +53,10 @@ template <class C> void launch_normalize_compressed(hipStream_t s, const uint32_
 // the normalisation is launched with
 template <class C> void launch_fixed_base(hipStream_t s, const uint8_t* scalars, size_t n, const uint32_t* table, int w,
                                           int nwin, uint32_t* proj_out, int* status, bool soa = false);
+// projective wire records X || Y || Z -> x || y records + identity flags (k_xyz_affine); prefix: n raw elements of scratch; a bad
+// record sets ST_BAD_POINT
+template <class C> void launch_xyz_affine(hipStream_t s, const uint8_t* xyz, size_t n, uint32_t* prefix, uint8_t* out_xy,
+                                          uint8_t* out_inf, int* status);
 template <class C> void launch_load_proj(hipStream_t s, const uint8_t* xyz, size_t n, uint32_t* proj_out, int* status);
 template <class C> void launch_point_sum(hipStream_t s, const uint8_t* xy, const uint8_t* inf, size_t n, uint32_t* proj_out,
                                          int* status);

@@ -163,8 +163,8 @@ where
     C::FieldBytesSize: ModulusSize,
     Aff<C>: AffineCoordinates<FieldRepr = FieldBytes<C>>,
 {
-    // to_affine per point (one inversion each on the CPU); a caller holding many projective points ships X || Y || Z
-    // to ecgpu_batch_normalize instead (BatchNormalize::batch_normalize, primeorder/src/projective.rs:452-478)
+    // to_affine per point (one inversion each on the CPU): only for points that arrive affine (ECDH public keys); every
+    // call site with projective points ships X || Y || Z (points_to_wire_xyz) and the device normalises
     let l = field_len::<C>();
     let (mut xy, mut inf) = (Vec::new(), Vec::new());
     for p in ps {
@@ -253,19 +253,19 @@ pub mod gpu {
     }
 
     /// `k[i] * P[i]` — batch form of `MulVartime::mul_vartime` (primeorder/src/projective.rs:888-921).
+    /// The points go in as they are, `X || Y || Z` (`ecgpu_batch_mul_xyz`: `to_affine` runs on the device).
     pub fn batch_mul_vartime<C: GpuCurve>(terms: &[(Proj<C>, Sc<C>)]) -> Option<Vec<Proj<C>>>
     where
         C::FieldBytesSize: ModulusSize,
         Aff<C>: FromSec1Point<C> + AffineCoordinates<FieldRepr = FieldBytes<C>>,
+        Proj<C>: ProjectiveCoordinates<C>,
     {
         let eng = ENGINE.as_ref()?.lock().ok()?;
         let (n, l) = (terms.len(), field_len::<C>());
         let scalars = scalars_to_wire::<C>(terms.iter().map(|t| t.1));
-        let (pts, pinf) = points_to_wire::<C>(terms.iter().map(|t| t.0));
+        let pts = points_to_wire_xyz::<C>(terms.iter().map(|t| t.0));
         let (mut xy, mut inf) = (vec![0u8; n * 2 * l], vec![0u8; n]);
-        check(unsafe {
-            ecgpu_batch_mul(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(), inf.as_mut_ptr())
-        })?;
+        check(unsafe { ecgpu_batch_mul_xyz(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), inf.as_mut_ptr()) })?;
         Some(xy.chunks(2 * l).zip(inf).map(|(c, f)| point_from_wire::<C>(c, f)).collect())
     }
 
@@ -374,49 +374,50 @@ pub mod gpu {
 
     /// `sum_i k[i] * P[i]` — `LinearCombination::lincomb_vartime` (Pippenger instead of Straus; same group element).
     /// One GPU up to NODE_MIN_TERMS terms, all GPUs of the node beyond (ecgpu_group_msm: term shards, one exchange of
-    /// per-window partial sums over xGMI, one combining step).
+    /// per-window partial sums over xGMI, one combining step).  The points go in as they are, `X || Y || Z`
+    /// (`ecgpu_group_msm_xyz` / `ecgpu_msm_xyz`: `to_affine` runs on the device).
     pub fn lincomb_vartime<C: GpuCurve>(terms: &[(Proj<C>, Sc<C>)]) -> Option<Proj<C>>
     where
         C::FieldBytesSize: ModulusSize,
         Aff<C>: FromSec1Point<C> + AffineCoordinates<FieldRepr = FieldBytes<C>>,
+        Proj<C>: ProjectiveCoordinates<C>,
     {
         let (n, l) = (terms.len(), field_len::<C>());
         let scalars = scalars_to_wire::<C>(terms.iter().map(|t| t.1));
-        let (pts, pinf) = points_to_wire::<C>(terms.iter().map(|t| t.0));
+        let pts = points_to_wire_xyz::<C>(terms.iter().map(|t| t.0));
         let (mut xy, mut inf) = (vec![0u8; 2 * l], 0u8);
         if n >= NODE_MIN_TERMS {
             if let Some(node) = NODE.as_ref().and_then(|m| m.lock().ok()) {
                 // a failed group call (one GPU of the node gone, out of memory) falls through to the single-GPU engine
-                if check(unsafe {
-                    ecgpu_group_msm(node.0, C::ID, scalars.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(), &mut inf)
-                })
-                .is_some()
+                if check(unsafe { ecgpu_group_msm_xyz(node.0, C::ID, scalars.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), &mut inf) })
+                    .is_some()
                 {
                     return Some(point_from_wire::<C>(&xy, inf));
                 }
             }
         }
         let eng = ENGINE.as_ref()?.lock().ok()?;
-        check(unsafe { ecgpu_msm(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(), &mut inf) })?;
+        check(unsafe { ecgpu_msm_xyz(eng.0, C::ID, scalars.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), &mut inf) })?;
         Some(point_from_wire::<C>(&xy, inf))
     }
 
     /// `a[i] * G + b[i] * P[i]` — batch form of `mul_by_generator_and_mul_add_vartime`
-    /// (primeorder/src/mul_backend.rs:29-40, k256/src/arithmetic/mul.rs:303-310).
+    /// (primeorder/src/mul_backend.rs:29-40, k256/src/arithmetic/mul.rs:303-310).  The points go in as they are,
+    /// `X || Y || Z` (`ecgpu_batch_mul_base_and_mul_add_xyz`: `to_affine` runs on the device).
     pub fn batch_mul_by_generator_and_mul_add_vartime<C: GpuCurve>(abp: &[(Sc<C>, Sc<C>, Proj<C>)]) -> Option<Vec<Proj<C>>>
     where
         C::FieldBytesSize: ModulusSize,
         Aff<C>: FromSec1Point<C> + AffineCoordinates<FieldRepr = FieldBytes<C>>,
+        Proj<C>: ProjectiveCoordinates<C>,
     {
         let eng = ENGINE.as_ref()?.lock().ok()?;
         let (n, l) = (abp.len(), field_len::<C>());
         let a = scalars_to_wire::<C>(abp.iter().map(|t| t.0));
         let b = scalars_to_wire::<C>(abp.iter().map(|t| t.1));
-        let (pts, pinf) = points_to_wire::<C>(abp.iter().map(|t| t.2));
+        let pts = points_to_wire_xyz::<C>(abp.iter().map(|t| t.2));
         let (mut xy, mut inf) = (vec![0u8; n * 2 * l], vec![0u8; n]);
         check(unsafe {
-            ecgpu_batch_mul_base_and_mul_add(eng.0, C::ID, a.as_ptr(), b.as_ptr(), pts.as_ptr(), pinf.as_ptr(), n, xy.as_mut_ptr(),
-                                             inf.as_mut_ptr())
+            ecgpu_batch_mul_base_and_mul_add_xyz(eng.0, C::ID, a.as_ptr(), b.as_ptr(), pts.as_ptr(), n, xy.as_mut_ptr(), inf.as_mut_ptr())
         })?;
         Some(xy.chunks(2 * l).zip(inf).map(|(c, f)| point_from_wire::<C>(c, f)).collect())
     }

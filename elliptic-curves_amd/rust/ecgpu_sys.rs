@@ -615,6 +615,89 @@ unsafe extern "C" {
         d_out_xy: *mut c_void,
         d_out_inf: *mut c_void,
     ) -> c_int;
+    pub fn ecgpu_batch_mul_xyz(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_batch_mul_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        d_out_xy: *mut c_void,
+        d_out_inf: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_msm_xyz(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_msm_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        d_out_xy: *mut c_void,
+        d_out_inf: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_batch_mul_base_and_mul_add_xyz(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        a_scalars: *const u8,
+        b_scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_batch_mul_base_and_mul_add_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_a_scalars: *const c_void,
+        d_b_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        d_out_xy: *mut c_void,
+        d_out_inf: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_msm_parts_xyz_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_scalars: *const c_void,
+        d_points_xyz: *const c_void,
+        n: usize,
+        plan_terms: usize,
+        d_parts: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_group_msm_xyz(
+        group: *mut EcgpuGroup,
+        curve: c_int,
+        scalars: *const u8,
+        points_xyz: *const u8,
+        n: usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_group_msm_xyz_dev(
+        group: *mut EcgpuGroup,
+        curve: c_int,
+        d_scalars: *const *const c_void,
+        d_points_xyz: *const *const c_void,
+        n_per_device: *const usize,
+        out_xy: *mut u8,
+        out_inf: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_msm_compressed(
         ctx: *mut EcgpuCtx,
         curve: c_int,

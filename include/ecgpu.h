@@ -19,7 +19,8 @@
  *             (primeorder/src/affine.rs:106-112) + optional n-byte identity flags
  *             (`AffinePoint::infinity`, k256/src/arithmetic/affine.rs:45-49); NULL flags = none.
  *             The identity is encoded as x = y = 0 with flag 1 on output.
- *   projective inputs (ecgpu_batch_normalize, ecgpu_batch_mul_ct_xyz, ecgpu_lincomb_ct_xyz): n * 3L bytes X || Y || Z,
+ *   projective inputs (ecgpu_batch_normalize, the *_xyz entry points: ecgpu_batch_mul[_ct]_xyz, ecgpu_msm_xyz,
+ *             ecgpu_lincomb_ct_xyz, ecgpu_batch_mul_base_and_mul_add_xyz, ecgpu_msm_parts_xyz_dev, ecgpu_group_msm_xyz): n * 3L bytes X || Y || Z,
  *             canonical big-endian, homogeneous (x = X/Z, y = Y/Z: `ProjectivePoint`, k256/src/arithmetic/projective.rs:40-45,
  *             primeorder/src/projective.rs:49-53); Z = 0 is the identity whatever X and Y are (`to_affine`); no flag array.
  *   ECGPU_BIGN256 (bign-curve256v1, `bignp256`) is the exception to "big-endian": its field elements and scalars travel
@@ -41,7 +42,9 @@
  * kernels' duration and memory access pattern depend on the scalar).  Those stand behind the reference's `*_vartime` names —
  * `MulVartime::mul_vartime` (primeorder/src/projective.rs:888-921), `LinearCombination::lincomb_vartime` (:498-510,
  * k256/src/arithmetic/mul.rs:100-108), `MulByGeneratorVartime::{mul_by_generator_vartime,
- * mul_by_generator_and_mul_add_vartime}` (:923-940, k256 mul.rs:205-232,296-310) — and is meant for PUBLIC scalars:
+ * mul_by_generator_and_mul_add_vartime}` (:923-940, k256 mul.rs:205-232,296-310) — with affine points, or with the reference's
+ * `ProjectivePoint` itself through the *_xyz forms (below; primeorder/src/projective.rs:480-511,888-940, k256 mul.rs:84-109,296-310:
+ * `lincomb_vartime`, `mul_vartime`, `mul_by_generator_and_mul_add_vartime` take projective points) — and is meant for PUBLIC scalars:
  * signature verification, MSMs over public data, batch derivation of public values.  It is NOT a replacement for the
  * constant-time `Mul` / `mul_by_generator` / `lincomb` (primeorder/src/projective.rs:532-557, tables/lookup.rs:43-65)
  * when the scalar is a long-term secret and an attacker can observe the device (timing of a shared GPU, its memory
@@ -559,6 +562,38 @@ int ecgpu_lincomb_ct_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, cons
                          uint8_t *out_inf);
 int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, void *d_out_xy,
                              void *d_out_inf);
+
+/* The variable-time forms with projective points: ecgpu_batch_mul, ecgpu_msm, ecgpu_batch_mul_base_and_mul_add,
+ * ecgpu_msm_parts_dev and ecgpu_group_msm with point i given as the record X || Y || Z of the wire format above (3L bytes, no flag
+ * array), as the reference's `mul_vartime`, `lincomb_vartime` and `mul_by_generator_and_mul_add_vartime` take a `ProjectivePoint`.
+ * For every input the results and the return code are those of `to_affine` applied to each record (ecgpu_batch_normalize)
+ * followed by the affine form, under the rule of the _ct_xyz forms above: X, Y or Z >= p (Z = 0 included), and a record with
+ * Z != 0 and Y^2 Z != X^3 + a X Z^2 + b Z^3, fail the call with ECGPU_ERR_POINT; Z = 0 is the identity.  The records are
+ * normalised on the device (k_xyz_affine: one field inversion per lane of up to 64 records, Montgomery's trick; Z = 0 and Z = 1
+ * skip the product chain) into the context's scratch, and the affine pipeline runs unchanged behind that.  Host-pointer forms
+ * pipeline at the sizes of their twins with 3L-byte records (ecgpu_msm_xyz from 2^23 terms in chunks of 2^22, the batch calls
+ * from 2^19 units); `_dev` bases must be 16-byte aligned; errors are deferred on asynchronous contexts.  MSM lanes
+ * (ecgpu_set_msm_lanes): an ecgpu_msm_xyz_dev / ecgpu_msm_parts_xyz_dev that goes to a lane converts its records on that lane,
+ * into buffers of the lane, beside the MSM before it — the caller's X || Y || Z array belongs to the lane as an affine one would;
+ * the small-MSM path (no lane) and the other calls convert on the context's stream, which first waits for the lanes. */
+int ecgpu_batch_mul_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const uint8_t *points_xyz, size_t n, uint8_t *out_xy,
+                        uint8_t *out_inf);
+int ecgpu_batch_mul_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, void *d_out_xy,
+                            void *d_out_inf);
+int ecgpu_msm_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const uint8_t *points_xyz, size_t n, uint8_t *out_xy,
+                  uint8_t *out_inf);
+int ecgpu_msm_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, void *d_out_xy,
+                      void *d_out_inf);
+int ecgpu_batch_mul_base_and_mul_add_xyz(ecgpu_ctx *ctx, int curve, const uint8_t *a_scalars, const uint8_t *b_scalars,
+                                         const uint8_t *points_xyz, size_t n, uint8_t *out_xy, uint8_t *out_inf);
+int ecgpu_batch_mul_base_and_mul_add_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_a_scalars, const void *d_b_scalars,
+                                             const void *d_points_xyz, size_t n, void *d_out_xy, void *d_out_inf);
+int ecgpu_msm_parts_xyz_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xyz, size_t n, size_t plan_terms,
+                            void *d_parts);
+int ecgpu_group_msm_xyz(ecgpu_group *group, int curve, const uint8_t *scalars, const uint8_t *points_xyz, size_t n, uint8_t *out_xy,
+                        uint8_t *out_inf);
+int ecgpu_group_msm_xyz_dev(ecgpu_group *group, int curve, const void *const *d_scalars, const void *const *d_points_xyz,
+                            const size_t *n_per_device, uint8_t *out_xy, uint8_t *out_inf);
 
 /* Compressed points INTO the path (callers hold 33-byte SEC1 keys).  Like ecgpu_msm / ecgpu_batch_mul with
  * point i given as points_x[i] (L bytes, the curve's wire order) + points_tag[i]: 0x02 / 0x03 = the point with that x and even /

@@ -26,7 +26,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "elliptic-curves_amd", "csrc")
-HASHING = ("k_ecdsa_hash_msg", "k_sm2dsa_hash_msg", "k_schnorr_prepare_raw")
+HASHING = ("k_ecdsa_hash_msg", "k_sm2dsa_hash_msg", "k_schnorr_prepare_raw", "k_bign_hash_msg")
 
 
 def kernels(asm):
