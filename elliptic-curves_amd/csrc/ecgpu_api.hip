@@ -249,7 +249,7 @@ struct SyncScope {
     ecgpu_ctx* ctx;
     bool was;
     int rc = ECGPU_OK;      // a failed drain (sticky device fault of the queued work, failed copy): the entry point returns it
-    explicit SyncScope(ecgpu_ctx* c) : ctx(c), was(c->async) {
+    explicit SyncScope(ecgpu_ctx* c) : ctx(c), was(c && c->async) {        // (no context: nothing to do, HostCall reports it)
         if (was) {
             rc = drain(ctx);
             ctx->async = false;
@@ -269,19 +269,19 @@ struct SyncScope {
 // is zeroed behind its last kernel (stream-ordered), and `staging` also clears the copies a host-pointer call made of the
 // caller's scalars and results.  The caller's own buffers are the caller's to wipe; ecgpu_wipe does the same on request.
 enum : int { WIPE_SCRATCH = 1, WIPE_EC = 2, WIPE_STAGING = 4 };
+void wipe_bufs(ecgpu_ctx* ctx, std::initializer_list<DevBuf*> bufs) {
+    // what has been asked of a buffer since its last wipe, not its capacity: after one 2^20-term batch the scratch holds
+    // ~170 MB, and zeroing all of it behind every later 1,024-scalar `_ct` call (or every chunk of a pipelined one) cost tens
+    // of microseconds per call
+    for (DevBuf* b : bufs) {
+        if (b->p && b->dirty) (void)hipMemsetAsync(b->p, 0, b->dirty < b->cap ? b->dirty : b->cap, ctx->stream);
+        b->dirty = 0;
+    }
+}
 void wipe_scratch(ecgpu_ctx* ctx, int what) {
-    auto clear = [&](std::initializer_list<DevBuf*> bufs) {
-        // what has been asked of a buffer since its last wipe, not its capacity: after one 2^20-term batch the scratch holds
-        // ~170 MB, and zeroing all of it behind every later 1,024-scalar `_ct` call (or every chunk of a pipelined one) cost tens
-        // of microseconds per call
-        for (DevBuf* b : bufs) {
-            if (b->p && b->dirty) (void)hipMemsetAsync(b->p, 0, b->dirty < b->cap ? b->dirty : b->cap, ctx->stream);
-            b->dirty = 0;
-        }
-    };
-    if (what & WIPE_SCRATCH) clear({&ctx->proj, &ctx->prefix});
-    if (what & WIPE_EC) clear({&ctx->ec_xy, &ctx->ec_inf});
-    if (what & WIPE_STAGING) clear({&ctx->in0, &ctx->in3, &ctx->out0, &ctx->out1});
+    if (what & WIPE_SCRATCH) wipe_bufs(ctx, {&ctx->proj, &ctx->prefix});
+    if (what & WIPE_EC) wipe_bufs(ctx, {&ctx->ec_xy, &ctx->ec_inf});
+    if (what & WIPE_STAGING) wipe_bufs(ctx, {&ctx->in0, &ctx->in3, &ctx->out0, &ctx->out1});
 }
 struct CtWipe {
     ecgpu_ctx* ctx;
@@ -1126,8 +1126,11 @@ inline size_t msm_pipe_chunk() {
     return MSM_PIPE_CHUNK;
 }
 
-struct PipeIn { const uint8_t* host; DevBuf* dev; size_t unit; };
-struct PipeOut { uint8_t* host; DevBuf* dev; size_t unit; };
+// One array of a host-pointer call: the caller's memory, the context buffer it is staged in, bytes per element.  `secret`: it
+// holds a secret of a uniform-schedule call or a value derived from one, and `staged` zeroes the buffer behind the call.
+struct PipeIn { const uint8_t* host; DevBuf* dev; size_t unit; bool secret = false; };
+struct PipeOut { uint8_t* host; DevBuf* dev; size_t unit; bool secret = false; };
+constexpr bool SECRET = true;
 
 template <class F>
 int pipelined(ecgpu_ctx* ctx, size_t n, const std::vector<PipeIn>& ins, const std::vector<PipeOut>& outs, F&& compute,
@@ -1241,6 +1244,109 @@ int arg_error(ecgpu_ctx* ctx, const char* fn) {
 int curve_error(ecgpu_ctx* ctx, const char* fn) {
     if (ctx) ctx->err = std::string(fn) + ": unknown curve id, or the operation does not exist for this curve";
     return ECGPU_ERR_CURVE;
+}
+
+// ---- the one staging path of the host-pointer entry points -------------------------------------------------------------
+// What every such entry point begins with, in the order of its early returns: no (usable) context -> ECGPU_ERR_ARG without a
+// message; the queued work of an asynchronous context drained (SyncScope, which restores the mode when the call ends) -> a
+// failed drain's code; the curve's field bytes L -> curve_error; the entry point's own condition (`bad`) -> arg_error.  The
+// messages name `fn`, the public function.
+struct HostCall {
+    ecgpu_ctx* ctx;
+    const char* fn;
+    int rc;
+    SyncScope sync;
+    size_t L;
+    HostCall(ecgpu_ctx* c, const char* fn_, int curve)
+        : ctx(c), fn(fn_), rc(check_ctx(c) ? ECGPU_OK : ECGPU_ERR_ARG), sync(rc == ECGPU_OK ? c : nullptr), L(ecgpu_field_bytes(curve)) {
+        if (rc == ECGPU_OK) rc = sync.rc != ECGPU_OK ? sync.rc : L ? (int)ECGPU_OK : curve_error(ctx, fn);
+    }
+    bool bad(bool args_bad) {
+        if (rc == ECGPU_OK && args_bad) rc = arg_error(ctx, fn);
+        return rc != ECGPU_OK;
+    }
+};
+
+inline const void* piece_of(const PipeIn& a, size_t off) { return a.host ? (const uint8_t*)a.dev->p + off * a.unit : nullptr; }
+
+// the uniform-schedule forms keep their scalars and results in the staging set of wipe_scratch; a list that marks a buffer
+// outside that set gets it zeroed all the same
+struct StagedWipe {
+    ecgpu_ctx* ctx;
+    const std::vector<PipeIn>& ins;
+    const std::vector<PipeOut>& outs;
+    ~StagedWipe() {
+        std::vector<DevBuf*> marked;
+        for (auto& a : ins) if (a.secret) marked.push_back(a.dev);
+        for (auto& o : outs) if (o.secret) marked.push_back(o.dev);
+        for (DevBuf* b : marked) wipe_bufs(ctx, {b});
+        if (!marked.empty()) wipe_scratch(ctx, WIPE_STAGING);
+    }
+};
+
+// Stage in, run the `_dev` entry, stage out.  An entry point states its arrays once (`ins`, `outs`) and its device call once:
+// call(in, out, m) receives the device address of each array's first element of the piece it is given (in list order;
+// nullptr for an input the caller left out: host == nullptr, which is not staged) and the piece's element count m.  From
+// PIPE_MIN elements on a STAGE_BATCH call is `pipelined` piece by piece; otherwise everything goes up on the context's stream,
+// the call runs once (for n == 0 too: it may build a table, and a reducing call writes the identity) and the results come
+// down.  Whatever way the call leaves, the buffers marked `secret` are zeroed behind its last kernel.
+enum StageMode {
+    STAGE_BATCH,     // n independent elements in, n records out
+    STAGE_WHOLE,     // the same, never cut (ecgpu_batch_normalize, the GLV and self-test entry points)
+    STAGE_REDUCE     // n elements in, one record out
+};
+template <class F>
+int staged(ecgpu_ctx* ctx, size_t n, const std::vector<PipeIn>& ins, const std::vector<PipeOut>& outs, F&& call,
+           StageMode mode = STAGE_BATCH) {
+    StagedWipe wipe{ctx, ins, outs};
+    std::vector<const void*> in(ins.size());
+    std::vector<void*> out(outs.size());
+    auto piece = [&](size_t off, size_t m) {
+        for (size_t i = 0; i < ins.size(); i++) in[i] = piece_of(ins[i], off);
+        for (size_t i = 0; i < outs.size(); i++) out[i] = (uint8_t*)outs[i].dev->p + off * outs[i].unit;
+        return call(in.data(), out.data(), m);
+    };
+    if (mode == STAGE_BATCH && n >= PIPE_MIN) return pipelined(ctx, n, ins, outs, piece);
+    const size_t nout = mode == STAGE_REDUCE ? 1 : n;
+    int rc;
+    for (auto& a : ins) if (a.host && (rc = upload(ctx, *a.dev, a.host, n * a.unit)) != ECGPU_OK) return rc;
+    for (auto& o : outs) if ((rc = ensure(ctx, *o.dev, nout * o.unit + 16)) != ECGPU_OK) return rc;
+    if ((rc = piece(0, n)) != ECGPU_OK) return rc;
+    for (auto& o : outs) if ((rc = download(ctx, o.host, *o.dev, nout * o.unit)) != ECGPU_OK) return rc;
+    return ECGPU_OK;
+}
+
+// The host-pointer MSMs (result staged in out0 / out1).  partial(c, in, m, d_out_xy, d_out_inf) runs the internal MSM
+// template of curve `c` on the m terms at in[] (the arrays of `ins`, as for `staged`).
+template <class F>
+int msm_staged(ecgpu_ctx* ctx, int curve, size_t n, const std::vector<PipeIn>& ins, uint8_t* out_xy, uint8_t* out_inf, F&& partial) {
+    const size_t L = ecgpu_field_bytes(curve), pipe_chunk = msm_pipe_chunk();
+    if (n < 2 * pipe_chunk)
+        return staged(ctx, n, ins, {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+            return dispatch(curve, [&](auto c) { return partial(c, in, m, out[0], out[1]); });
+        }, STAGE_REDUCE);
+    // An MSM needs all of its terms before its sort can start, and 96 (144) bytes per term take longer to upload than
+    // the MSM takes to compute: sum_i k_i P_i is computed as one MSM per chunk of 2^22 terms, each under the upload of
+    // the next chunk, and the partial sums are added at the end.  The partial records sit at a pitch of 2L bytes
+    // (56 for p224, 132 for p521: not 16-byte multiples), so the internal implementations are called directly — the
+    // kernels of those curves use 4-byte / byte accesses; only the public *_dev entry points insist on 16-byte bases.
+    const size_t nparts = (n + pipe_chunk - 1) / pipe_chunk;
+    int rc;
+    if ((rc = ensure(ctx, ctx->out0, (nparts + 1) * 2 * L + 64)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->out1, nparts + 32)) != ECGPU_OK) return rc;
+    uint8_t* part_xy = (uint8_t*)ctx->out0.p + (2 * L + 15) / 16 * 16;          // [0] is the final result
+    uint8_t* part_inf = (uint8_t*)ctx->out1.p + 16;
+    return dispatch(curve, [&](auto c) -> int {
+        std::vector<const void*> in(ins.size());
+        int r = pipelined(ctx, n, ins, {}, [&](size_t off, size_t m) {
+            for (size_t i = 0; i < ins.size(); i++) in[i] = piece_of(ins[i], off);
+            return partial(c, in.data(), m, part_xy + off / pipe_chunk * 2 * L, part_inf + off / pipe_chunk);
+        }, pipe_chunk);
+        if (r != ECGPU_OK) return r;
+        if ((r = point_sum_dev<decltype(c)>(ctx, part_xy, part_inf, nparts, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return r;
+        if ((r = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return r;
+        return download(ctx, out_inf, ctx->out1, 1);
+    });
 }
 
 }  // namespace
@@ -2030,31 +2136,16 @@ int ecgpu_batch_decompress_dev(ecgpu_ctx* ctx, int curve, const void* d_xs, cons
 }
 
 // ---- host-pointer entry points ----
+// Each one is: the preamble with its own NULL-argument condition (HostCall), the list of its arrays, its `_dev` call (staged).
 
-// (ct: the uniform-schedule form; the host-side plumbing is the same)
+// (ct: the uniform-schedule form; the host-side plumbing is the same, its scalars and results are marked for the wipe)
 static int batch_mul_base_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, size_t n, uint8_t* out_xy, uint8_t* out_inf,
                                bool ct, const char* fn) {
+    HostCall h(ctx, fn, curve);
+    if (h.bad(n && (!scalars || !out_xy))) return h.rc;
     const auto dev = ct ? ecgpu_batch_mul_base_ct_dev : ecgpu_batch_mul_base_dev;
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, fn);
-    if (n && (!scalars || !out_xy)) return arg_error(ctx, fn);
-    CtWipe wipe(ctx, ct ? WIPE_STAGING : 0);          // (after everything below, before SyncScope restores the mode)
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}}, {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, m,
-                                                             (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = dev(ctx, curve, ctx->in0.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L, ct}}, {{out_xy, &ctx->out0, 2 * h.L, ct}, {out_inf, &ctx->out1, 1, ct}},
+                  [&](auto in, auto out, size_t m) { return dev(ctx, curve, in[0], m, out[0], out[1]); });
 }
 
 int ecgpu_batch_mul_base(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, size_t n, uint8_t* out_xy, uint8_t* out_inf) {
@@ -2066,58 +2157,24 @@ int ecgpu_batch_mul_base_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, s
 
 int ecgpu_batch_mul_base_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, size_t n, uint8_t* out_x,
                                     uint8_t* out_tag) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!scalars || !out_x || !out_tag)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}}, {{out_x, &ctx->out0, L}, {out_tag, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-            return ecgpu_batch_mul_base_compressed_dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, m, (uint8_t*)ctx->out0.p + off * L,
-                                                       (uint8_t*)ctx->out1.p + off);
-        });
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_batch_mul_base_compressed_dev(ctx, curve, ctx->in0.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_x, ctx->out0, n * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_tag, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!scalars || !out_x || !out_tag))) return h.rc;
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L}}, {{out_x, &ctx->out0, h.L}, {out_tag, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_batch_mul_base_compressed_dev(ctx, curve, in[0], m, out[0], out[1]); });
 }
 
 // the host-pointer batch multiplication over either point record: affine x || y (+ optional identity flags) for
 // ecgpu_batch_mul[_ct], projective X || Y || Z (3L bytes, no flags) for ecgpu_batch_mul[_ct]_xyz
 static int batch_mul_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points, const uint8_t* points_inf,
                           size_t n, uint8_t* out_xy, uint8_t* out_inf, bool ct, bool xyz, const char* fn) {
-    const auto dev = [&](const void* k, const void* p, const void* pi, size_t m, void* o, void* oi) {
-        if (xyz) return ct ? ecgpu_batch_mul_ct_xyz_dev(ctx, curve, k, p, m, o, oi) : ecgpu_batch_mul_xyz_dev(ctx, curve, k, p, m, o, oi);
-        return ct ? ecgpu_batch_mul_ct_dev(ctx, curve, k, p, pi, m, o, oi) : ecgpu_batch_mul_dev(ctx, curve, k, p, pi, m, o, oi);
-    };
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, fn);
-    if (n && (!scalars || !points || !out_xy)) return arg_error(ctx, fn);
-    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
-    CtWipe wipe(ctx, ct ? WIPE_STAGING : 0);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
-                         {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return dev((uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
-                                        points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, (uint8_t*)ctx->out0.p + off * 2 * L,
-                                        (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points, n * PB)) != ECGPU_OK) return rc;
-    if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = dev(ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    HostCall h(ctx, fn, curve);
+    if (h.bad(n && (!scalars || !points || !out_xy))) return h.rc;
+    const size_t PB = (xyz ? 3 : 2) * h.L;           // bytes per point record
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L, ct}, {points, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L, ct}, {out_inf, &ctx->out1, 1, ct}}, [&](auto in, auto out, size_t m) {
+                      if (xyz) return (ct ? ecgpu_batch_mul_ct_xyz_dev : ecgpu_batch_mul_xyz_dev)(ctx, curve, in[0], in[1], m, out[0], out[1]);
+                      return (ct ? ecgpu_batch_mul_ct_dev : ecgpu_batch_mul_dev)(ctx, curve, in[0], in[1], in[2], m, out[0], out[1]);
+                  });
 }
 
 int ecgpu_batch_mul(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
@@ -2142,53 +2199,13 @@ int ecgpu_batch_mul_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const
 // X || Y || Z (3L bytes, no flags) for ecgpu_msm_xyz
 static int msm_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
                     size_t n, uint8_t* out_xy, uint8_t* out_inf, bool xyz, const char* fn) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, fn);
-    if (!out_xy || (n && (!scalars || !points_xy))) return arg_error(ctx, fn);
-    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
-    int rc;
-    const size_t pipe_chunk = msm_pipe_chunk();
-    if (n >= 2 * pipe_chunk) {
-        // An MSM needs all of its terms before its sort can start, and 96 (144) bytes per term take longer to upload than
-        // the MSM takes to compute: sum_i k_i P_i is computed as one MSM per chunk of 2^22 terms, each under the upload of
-        // the next chunk, and the partial sums are added at the end.  The partial records sit at a pitch of 2L bytes
-        // (56 for p224, 132 for p521: not 16-byte multiples), so the internal implementations are called directly — the
-        // kernels of those curves use 4-byte / byte accesses; only the public *_dev entry points insist on 16-byte bases.
-        const size_t nparts = (n + pipe_chunk - 1) / pipe_chunk;
-        if ((rc = ensure(ctx, ctx->out0, (nparts + 1) * 2 * L + 64)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->out1, nparts + 32)) != ECGPU_OK) return rc;
-        uint8_t* part_xy = (uint8_t*)ctx->out0.p + (2 * L + 15) / 16 * 16;          // [0] is the final result
-        uint8_t* part_inf = (uint8_t*)ctx->out1.p + 16;
-        return dispatch(curve, [&](auto c) -> int {
-            using C = decltype(c);
-            int r = pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}}, {},
-                              [&](size_t off, size_t m) {
-                                  const size_t j = off / pipe_chunk;
-                                  return msm_dev<C>(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
-                                                    points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, part_xy + j * 2 * L, part_inf + j,
-                                                    xyz);
-                              },
-                              pipe_chunk);
-            if (r != ECGPU_OK) return r;
-            if ((r = point_sum_dev<C>(ctx, part_xy, part_inf, nparts, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return r;
-            if ((r = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return r;
-            return download(ctx, out_inf, ctx->out1, 1);
-        });
-    }
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * PB)) != ECGPU_OK) return rc;
-    if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = xyz ? ecgpu_msm_xyz_dev(ctx, curve, ctx->in0.p, ctx->in1.p, n, ctx->out0.p, ctx->out1.p)
-                  : ecgpu_msm_dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
-                                  ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, 1);
+    HostCall h(ctx, fn, curve);
+    if (h.bad(!out_xy || (n && (!scalars || !points_xy)))) return h.rc;
+    const size_t PB = (xyz ? 3 : 2) * h.L;           // bytes per point record
+    return msm_staged(ctx, curve, n, {{scalars, &ctx->in0, h.L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}}, out_xy, out_inf,
+                      [&](auto c, auto in, size_t m, void* d_out_xy, void* d_out_inf) {
+                          return msm_dev<decltype(c)>(ctx, in[0], in[1], in[2], m, d_out_xy, d_out_inf, xyz);
+                      });
 }
 
 int ecgpu_msm(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf,
@@ -2202,147 +2219,56 @@ int ecgpu_msm_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8
 
 int ecgpu_lincomb_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
                      uint8_t* out_xy, uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (!out_xy || (n && (!scalars || !points_xy))) return arg_error(ctx, __func__);
-    CtWipe wipe(ctx, WIPE_STAGING);
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_lincomb_ct_dev(ctx, curve, ctx->in0.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
-                                   ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, 1);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(!out_xy || (n && (!scalars || !points_xy)))) return h.rc;
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L, SECRET}, {points_xy, &ctx->in1, 2 * h.L}, {points_inf, &ctx->in2, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L, SECRET}, {out_inf, &ctx->out1, 1, SECRET}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_lincomb_ct_dev(ctx, curve, in[0], in[1], in[2], m, out[0], out[1]);
+                  }, STAGE_REDUCE);
 }
 
 int ecgpu_lincomb_ct_xyz(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
                          uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (!out_xy || (n && (!scalars || !points_xyz))) return arg_error(ctx, __func__);
-    CtWipe wipe(ctx, WIPE_STAGING);
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xyz, n * 3 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_lincomb_ct_xyz_dev(ctx, curve, ctx->in0.p, ctx->in1.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, 1);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(!out_xy || (n && (!scalars || !points_xyz)))) return h.rc;
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L, SECRET}, {points_xyz, &ctx->in1, 3 * h.L}},
+                  {{out_xy, &ctx->out0, 2 * h.L, SECRET}, {out_inf, &ctx->out1, 1, SECRET}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_lincomb_ct_xyz_dev(ctx, curve, in[0], in[1], m, out[0], out[1]);
+                  }, STAGE_REDUCE);
 }
 
 int ecgpu_msm_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_x, const uint8_t* points_tag,
                          size_t n, uint8_t* out_xy, uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (!out_xy || (n && (!scalars || !points_x || !points_tag))) return arg_error(ctx, __func__);
-    int rc;
-    const size_t pipe_chunk = msm_pipe_chunk();
-    if (n >= 2 * pipe_chunk) {          // as ecgpu_msm: one partial MSM per chunk under the upload of the next, then a point sum
-        const size_t nparts = (n + pipe_chunk - 1) / pipe_chunk;
-        if ((rc = ensure(ctx, ctx->out0, (nparts + 1) * 2 * L + 64)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->out1, nparts + 32)) != ECGPU_OK) return rc;
-        uint8_t* part_xy = (uint8_t*)ctx->out0.p + (2 * L + 15) / 16 * 16;
-        uint8_t* part_inf = (uint8_t*)ctx->out1.p + 16;
-        return dispatch(curve, [&](auto c) -> int {
-            using C = decltype(c);
-            int r = pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_x, &ctx->in1, L}, {points_tag, &ctx->in2, 1}}, {},
-                              [&](size_t off, size_t m) {
-                                  const size_t j = off / pipe_chunk;
-                                  return msm_compressed_dev<C>(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * L,
-                                                               (uint8_t*)ctx->in2.p + off, m, part_xy + j * 2 * L, part_inf + j);
-                              },
-                              pipe_chunk);
-            if (r != ECGPU_OK) return r;
-            if ((r = point_sum_dev<C>(ctx, part_xy, part_inf, nparts, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return r;
-            if ((r = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return r;
-            return download(ctx, out_inf, ctx->out1, 1);
-        });
-    }
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_x, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, points_tag, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_msm_compressed_dev(ctx, curve, ctx->in0.p, ctx->in1.p, ctx->in2.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, 1);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(!out_xy || (n && (!scalars || !points_x || !points_tag)))) return h.rc;
+    return msm_staged(ctx, curve, n, {{scalars, &ctx->in0, h.L}, {points_x, &ctx->in1, h.L}, {points_tag, &ctx->in2, 1}}, out_xy, out_inf,
+                      [&](auto c, auto in, size_t m, void* d_out_xy, void* d_out_inf) {
+                          return msm_compressed_dev<decltype(c)>(ctx, in[0], in[1], in[2], m, d_out_xy, d_out_inf);
+                      });
 }
 
 int ecgpu_batch_mul_compressed(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_x, const uint8_t* points_tag,
                                size_t n, uint8_t* out_xy, uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!scalars || !points_x || !points_tag || !out_xy)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_x, &ctx->in1, L}, {points_tag, &ctx->in2, 1}},
-                         {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_batch_mul_compressed_dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L,
-                                                                   (uint8_t*)ctx->in1.p + off * L, (uint8_t*)ctx->in2.p + off, m,
-                                                                   (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_x, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, points_tag, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_batch_mul_compressed_dev(ctx, curve, ctx->in0.p, ctx->in1.p, ctx->in2.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!scalars || !points_x || !points_tag || !out_xy))) return h.rc;
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L}, {points_x, &ctx->in1, h.L}, {points_tag, &ctx->in2, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_batch_mul_compressed_dev(ctx, curve, in[0], in[1], in[2], m, out[0], out[1]);
+                  });
 }
 
 // the host-pointer aG + bP batch over either point record: affine x || y (+ optional identity flags) for
 // ecgpu_batch_mul_base_and_mul_add, projective X || Y || Z (3L bytes, no flags) for its _xyz form
 static int mul_add_host(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars, const uint8_t* points_xy,
                         const uint8_t* points_inf, size_t n, uint8_t* out_xy, uint8_t* out_inf, bool xyz, const char* fn) {
-    const auto dev = [&](const void* a, const void* b, const void* p, const void* pi, size_t m, void* o, void* oi) {
-        if (xyz) return ecgpu_batch_mul_base_and_mul_add_xyz_dev(ctx, curve, a, b, p, m, o, oi);
-        return ecgpu_batch_mul_base_and_mul_add_dev(ctx, curve, a, b, p, pi, m, o, oi);
-    };
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, fn);
-    if (n && (!a_scalars || !b_scalars || !points_xy || !out_xy)) return arg_error(ctx, fn);
-    const size_t PB = (xyz ? 3 : 2) * L;           // bytes per point record
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{a_scalars, &ctx->in0, L}, {b_scalars, &ctx->in3, L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
-                         {{out_xy, &ctx->out0, 2 * L}, {out_inf, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return dev((uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L, (uint8_t*)ctx->in1.p + off * PB,
-                                        points_inf ? (uint8_t*)ctx->in2.p + off : nullptr, m, (uint8_t*)ctx->out0.p + off * 2 * L,
-                                        (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, a_scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, b_scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * PB)) != ECGPU_OK) return rc;
-    if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = dev(ctx->in0.p, ctx->in3.p, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    HostCall h(ctx, fn, curve);
+    if (h.bad(n && (!a_scalars || !b_scalars || !points_xy || !out_xy))) return h.rc;
+    const size_t PB = (xyz ? 3 : 2) * h.L;           // bytes per point record
+    return staged(ctx, n, {{a_scalars, &ctx->in0, h.L}, {b_scalars, &ctx->in3, h.L}, {points_xy, &ctx->in1, PB}, {points_inf, &ctx->in2, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      if (xyz) return ecgpu_batch_mul_base_and_mul_add_xyz_dev(ctx, curve, in[0], in[1], in[2], m, out[0], out[1]);
+                      return ecgpu_batch_mul_base_and_mul_add_dev(ctx, curve, in[0], in[1], in[2], in[3], m, out[0], out[1]);
+                  });
 }
 
 int ecgpu_batch_mul_base_and_mul_add(ecgpu_ctx* ctx, int curve, const uint8_t* a_scalars, const uint8_t* b_scalars,
@@ -2357,249 +2283,97 @@ int ecgpu_batch_mul_base_and_mul_add_xyz(ecgpu_ctx* ctx, int curve, const uint8_
 
 int ecgpu_ecdsa_verify_batch(ecgpu_ctx* ctx, int curve, const uint8_t* z, const uint8_t* r, const uint8_t* s,
                              const uint8_t* q_xy, size_t n, int reject_high_s, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!z || !r || !s || !q_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{z, &ctx->in0, L}, {r, &ctx->in3, L}, {s, &ctx->in2, L}, {q_xy, &ctx->in1, 2 * L}}, {{ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return ecgpu_ecdsa_verify_batch_dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L,
-                                                                 (uint8_t*)ctx->in2.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L, m,
-                                                                 reject_high_s, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, z, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, r, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, s, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_ecdsa_verify_batch_dev(ctx, curve, ctx->in0.p, ctx->in3.p, ctx->in2.p, ctx->in1.p, n, reject_high_s,
-                                           ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!z || !r || !s || !q_xy || !ok))) return h.rc;
+    return staged(ctx, n, {{z, &ctx->in0, h.L}, {r, &ctx->in3, h.L}, {s, &ctx->in2, h.L}, {q_xy, &ctx->in1, 2 * h.L}}, {{ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_verify_batch_dev(ctx, curve, in[0], in[1], in[2], in[3], m, reject_high_s, out[0]);
+                  });
 }
 
+// (the message-level verifiers: with msg_len == 0 there is no message array, and the device entry receives nullptr for it)
 int ecgpu_ecdsa_verify_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* q_xy, const uint8_t* msgs, size_t msg_len, const uint8_t* sigs,
                                  size_t n, int reject_high_s, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!q_xy || !sigs || !ok || (msg_len && !msgs))) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{q_xy, &ctx->in1, 2 * L}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 2 * L}},
-                         {{ok, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_ecdsa_verify_msg_batch_dev(ctx, curve, (uint8_t*)ctx->in1.p + off * 2 * L,
-                                                                     msg_len ? (uint8_t*)ctx->in0.p + off * msg_len : nullptr, msg_len,
-                                                                     (uint8_t*)ctx->in3.p + off * 2 * L, m, reject_high_s, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in0, msgs, n * msg_len)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, sigs, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_ecdsa_verify_msg_batch_dev(ctx, curve, ctx->in1.p, ctx->in0.p, msg_len, ctx->in3.p, n, reject_high_s, ctx->out1.p)) !=
-        ECGPU_OK)
-        return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!q_xy || !sigs || !ok || (msg_len && !msgs)))) return h.rc;
+    return staged(ctx, n, {{q_xy, &ctx->in1, 2 * h.L}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 2 * h.L}},
+                  {{ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_verify_msg_batch_dev(ctx, curve, in[0], in[1], msg_len, in[2], m, reject_high_s, out[0]);
+                  });
 }
 
 int ecgpu_ecdsa_recover_batch(ecgpu_ctx* ctx, int curve, const uint8_t* z, const uint8_t* r, const uint8_t* s,
                               const uint8_t* recid, size_t n, int reject_high_s, uint8_t* out_xy, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!z || !r || !s || !recid || !out_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{z, &ctx->in0, L}, {r, &ctx->in3, L}, {s, &ctx->in1, L}, {recid, &ctx->in2, 1}},
-                         {{out_xy, &ctx->out0, 2 * L}, {ok, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_ecdsa_recover_batch_dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L,
-                                                                  (uint8_t*)ctx->in1.p + off * L, (uint8_t*)ctx->in2.p + off, m, reject_high_s,
-                                                                  (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, z, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, r, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, s, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, recid, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_ecdsa_recover_batch_dev(ctx, curve, ctx->in0.p, ctx->in3.p, ctx->in1.p, ctx->in2.p, n, reject_high_s, ctx->out0.p,
-                                            ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!z || !r || !s || !recid || !out_xy || !ok))) return h.rc;
+    return staged(ctx, n, {{z, &ctx->in0, h.L}, {r, &ctx->in3, h.L}, {s, &ctx->in1, h.L}, {recid, &ctx->in2, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_recover_batch_dev(ctx, curve, in[0], in[1], in[2], in[3], m, reject_high_s, out[0], out[1]);
+                  });
 }
 
 int ecgpu_sm2dsa_verify_batch(ecgpu_ctx* ctx, const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint8_t* q_xy, size_t n,
                               uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    const size_t L = 32;
-    if (n && (!e || !r || !s || !q_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{e, &ctx->in0, L}, {r, &ctx->in3, L}, {s, &ctx->in2, L}, {q_xy, &ctx->in1, 2 * L}}, {{ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return ecgpu_sm2dsa_verify_batch_dev(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L,
-                                                                  (uint8_t*)ctx->in2.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L, m,
-                                                                  (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, e, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, r, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, s, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_sm2dsa_verify_batch_dev(ctx, ctx->in0.p, ctx->in3.p, ctx->in2.p, ctx->in1.p, n, ctx->out1.p)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(n && (!e || !r || !s || !q_xy || !ok))) return h.rc;
+    return staged(ctx, n, {{e, &ctx->in0, h.L}, {r, &ctx->in3, h.L}, {s, &ctx->in2, h.L}, {q_xy, &ctx->in1, 2 * h.L}}, {{ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_sm2dsa_verify_batch_dev(ctx, in[0], in[1], in[2], in[3], m, out[0]); });
 }
 
 int ecgpu_sm2dsa_verify_msg_batch(ecgpu_ctx* ctx, const uint8_t* distid, size_t distid_len, const uint8_t* q_xy, const uint8_t* msgs,
                                   size_t msg_len, const uint8_t* sigs, size_t n, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    if (distid_len > 8191 || (distid_len && !distid) || (n && (!q_xy || !sigs || !ok || (msg_len && !msgs)))) return arg_error(ctx, __func__);
-    int rc;
-    if ((rc = upload(ctx, ctx->ec_id, distid, distid_len)) != ECGPU_OK) return rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{q_xy, &ctx->in1, 64}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 64}},
-                         {{ok, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_sm2dsa_verify_msg_batch_dev(ctx, ctx->ec_id.p, distid_len, (uint8_t*)ctx->in1.p + off * 64,
-                                                                      msg_len ? (uint8_t*)ctx->in0.p + off * msg_len : nullptr, msg_len,
-                                                                      (uint8_t*)ctx->in3.p + off * 64, m, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 64)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in0, msgs, n * msg_len)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, sigs, n * 64)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_sm2dsa_verify_msg_batch_dev(ctx, ctx->ec_id.p, distid_len, ctx->in1.p, ctx->in0.p, msg_len, ctx->in3.p, n, ctx->out1.p)) !=
-        ECGPU_OK)
-        return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(distid_len > 8191 || (distid_len && !distid) || (n && (!q_xy || !sigs || !ok || (msg_len && !msgs))))) return h.rc;
+    int rc = upload(ctx, ctx->ec_id, distid, distid_len);          // one identifier for the whole batch: not an array of the list
+    if (rc != ECGPU_OK) return rc;
+    return staged(ctx, n, {{q_xy, &ctx->in1, 64}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 64}},
+                  {{ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_sm2dsa_verify_msg_batch_dev(ctx, ctx->ec_id.p, distid_len, in[0], in[1], msg_len, in[2], m, out[0]);
+                  });
 }
 
 int ecgpu_bign_verify_batch(ecgpu_ctx* ctx, const uint8_t* h, const uint8_t* sigs, const uint8_t* q_xy, size_t n, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    if (n && (!h || !sigs || !q_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{h, &ctx->in0, 32}, {sigs, &ctx->in3, 48}, {q_xy, &ctx->in1, 64}}, {{ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return ecgpu_bign_verify_batch_dev(ctx, (uint8_t*)ctx->in0.p + off * 32, (uint8_t*)ctx->in3.p + off * 48,
-                                                                (uint8_t*)ctx->in1.p + off * 64, m, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, h, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, sigs, n * 48)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 64)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_bign_verify_batch_dev(ctx, ctx->in0.p, ctx->in3.p, ctx->in1.p, n, ctx->out1.p)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall call(ctx, __func__, ECGPU_BIGN256);
+    if (call.bad(n && (!h || !sigs || !q_xy || !ok))) return call.rc;
+    return staged(ctx, n, {{h, &ctx->in0, 32}, {sigs, &ctx->in3, 48}, {q_xy, &ctx->in1, 64}}, {{ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_bign_verify_batch_dev(ctx, in[0], in[1], in[2], m, out[0]); });
 }
 
 int ecgpu_bign_verify_msg_batch(ecgpu_ctx* ctx, const uint8_t* q_xy, const uint8_t* msgs, size_t msg_len, const uint8_t* sigs, size_t n,
                                 uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    if (n && (!q_xy || !sigs || !ok || (msg_len && !msgs))) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{q_xy, &ctx->in1, 64}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 48}},
-                         {{ok, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_bign_verify_msg_batch_dev(ctx, (uint8_t*)ctx->in1.p + off * 64,
-                                                                    msg_len ? (uint8_t*)ctx->in0.p + off * msg_len : nullptr, msg_len,
-                                                                    (uint8_t*)ctx->in3.p + off * 48, m, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in1, q_xy, n * 64)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in0, msgs, n * msg_len)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, sigs, n * 48)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_bign_verify_msg_batch_dev(ctx, ctx->in1.p, ctx->in0.p, msg_len, ctx->in3.p, n, ctx->out1.p)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, ECGPU_BIGN256);
+    if (h.bad(n && (!q_xy || !sigs || !ok || (msg_len && !msgs)))) return h.rc;
+    return staged(ctx, n, {{q_xy, &ctx->in1, 64}, {msg_len ? msgs : nullptr, &ctx->in0, msg_len}, {sigs, &ctx->in3, 48}},
+                  {{ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_bign_verify_msg_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0]);
+                  });
 }
 
 int ecgpu_schnorr_verify_batch(ecgpu_ctx* ctx, const uint8_t* e, const uint8_t* r, const uint8_t* s, const uint8_t* p_xy,
                                size_t n, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    const size_t L = 32;
-    if (n && (!e || !r || !s || !p_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{e, &ctx->in0, L}, {r, &ctx->in3, L}, {s, &ctx->in2, L}, {p_xy, &ctx->in1, 2 * L}}, {{ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return ecgpu_schnorr_verify_batch_dev(ctx, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in3.p + off * L,
-                                                                   (uint8_t*)ctx->in2.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L, m,
-                                                                   (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, e, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, r, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, s, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, p_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_schnorr_verify_batch_dev(ctx, ctx->in0.p, ctx->in3.p, ctx->in2.p, ctx->in1.p, n, ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, ECGPU_K256);
+    if (h.bad(n && (!e || !r || !s || !p_xy || !ok))) return h.rc;
+    return staged(ctx, n, {{e, &ctx->in0, h.L}, {r, &ctx->in3, h.L}, {s, &ctx->in2, h.L}, {p_xy, &ctx->in1, 2 * h.L}}, {{ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_schnorr_verify_batch_dev(ctx, in[0], in[1], in[2], in[3], m, out[0]); });
 }
 
 int ecgpu_schnorr_verify_raw_batch(ecgpu_ctx* ctx, const uint8_t* pk_x, const uint8_t* msgs, size_t msg_len, const uint8_t* sigs,
                                    size_t n, uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    if (n && (!pk_x || !sigs || !ok || (msg_len && !msgs))) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{pk_x, &ctx->in0, 32}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {sigs, &ctx->in3, 64}},
-                         {{ok, &ctx->out1, 1}}, [&](size_t off, size_t m) {
-                             return ecgpu_schnorr_verify_raw_batch_dev(ctx, (uint8_t*)ctx->in0.p + off * 32,
-                                                                       msg_len ? (uint8_t*)ctx->in1.p + off * msg_len : nullptr, msg_len,
-                                                                       (uint8_t*)ctx->in3.p + off * 64, m, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, pk_x, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, msgs, n * msg_len)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in3, sigs, n * 64)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_schnorr_verify_raw_batch_dev(ctx, ctx->in0.p, ctx->in1.p, msg_len, ctx->in3.p, n, ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, ECGPU_K256);
+    if (h.bad(n && (!pk_x || !sigs || !ok || (msg_len && !msgs)))) return h.rc;
+    return staged(ctx, n, {{pk_x, &ctx->in0, 32}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {sigs, &ctx->in3, 64}},
+                  {{ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_schnorr_verify_raw_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0]);
+                  });
 }
 
 static int batch_ecdh_host(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, size_t n, uint8_t* out_x,
                            uint8_t* ok, bool ct, const char* fn) {
+    HostCall h(ctx, fn, curve);
+    if (h.bad(n && (!scalars || !points_xy || !out_x || !ok))) return h.rc;
     const auto dev = ct ? ecgpu_batch_ecdh_ct_dev : ecgpu_batch_ecdh_dev;
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, fn);
-    if (n && (!scalars || !points_xy || !out_x || !ok)) return arg_error(ctx, fn);
-    CtWipe wipe(ctx, ct ? WIPE_STAGING : 0);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{scalars, &ctx->in0, L}, {points_xy, &ctx->in1, 2 * L}}, {{out_x, &ctx->out0, L}, {ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in1.p + off * 2 * L, m,
-                                                         (uint8_t*)ctx->out0.p + off * L, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, scalars, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = dev(ctx, curve, ctx->in0.p, ctx->in1.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_x, ctx->out0, n * L)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    return staged(ctx, n, {{scalars, &ctx->in0, h.L, ct}, {points_xy, &ctx->in1, 2 * h.L}}, {{out_x, &ctx->out0, h.L, ct}, {ok, &ctx->out1, 1, ct}},
+                  [&](auto in, auto out, size_t m) { return dev(ctx, curve, in[0], in[1], m, out[0], out[1]); });
 }
 
 int ecgpu_batch_ecdh(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const uint8_t* points_xy, size_t n, uint8_t* out_x, uint8_t* ok) {
@@ -2612,132 +2386,72 @@ int ecgpu_batch_ecdh_ct(ecgpu_ctx* ctx, int curve, const uint8_t* scalars, const
 
 int ecgpu_batch_decompress(ecgpu_ctx* ctx, int curve, const uint8_t* xs, const uint8_t* y_is_odd, size_t n, uint8_t* out_xy,
                            uint8_t* ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!xs || !y_is_odd || !out_xy || !ok)) return arg_error(ctx, __func__);
-    int rc;
-    if (n >= PIPE_MIN)
-        return pipelined(ctx, n, {{xs, &ctx->in0, L}, {y_is_odd, &ctx->in2, 1}}, {{out_xy, &ctx->out0, 2 * L}, {ok, &ctx->out1, 1}},
-                         [&](size_t off, size_t m) {
-                             return ecgpu_batch_decompress_dev(ctx, curve, (uint8_t*)ctx->in0.p + off * L, (uint8_t*)ctx->in2.p + off, m,
-                                                               (uint8_t*)ctx->out0.p + off * 2 * L, (uint8_t*)ctx->out1.p + off);
-                         });
-    if ((rc = upload(ctx, ctx->in0, xs, n * L)) != ECGPU_OK) return rc;
-    if ((rc = upload(ctx, ctx->in2, y_is_odd, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_batch_decompress_dev(ctx, curve, ctx->in0.p, ctx->in2.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, ok, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!xs || !y_is_odd || !out_xy || !ok))) return h.rc;
+    return staged(ctx, n, {{xs, &ctx->in0, h.L}, {y_is_odd, &ctx->in2, 1}}, {{out_xy, &ctx->out0, 2 * h.L}, {ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_batch_decompress_dev(ctx, curve, in[0], in[1], m, out[0], out[1]); });
 }
 
 int ecgpu_batch_normalize(ecgpu_ctx* ctx, int curve, const uint8_t* points_xyz, size_t n, uint8_t* out_xy,
                           uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!points_xyz || !out_xy)) return arg_error(ctx, __func__);
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, points_xyz, n * 3 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_batch_normalize_dev(ctx, curve, ctx->in0.p, n, ctx->out0.p, ctx->out1.p)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!points_xyz || !out_xy))) return h.rc;
+    return staged(ctx, n, {{points_xyz, &ctx->in0, 3 * h.L}}, {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_batch_normalize_dev(ctx, curve, in[0], m, out[0], out[1]); }, STAGE_WHOLE);
 }
 
 int ecgpu_point_sum(ecgpu_ctx* ctx, int curve, const uint8_t* points_xy, const uint8_t* points_inf, size_t n,
                     uint8_t* out_xy, uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (!out_xy || (n && !points_xy)) return arg_error(ctx, __func__);
-    int rc;
-    if ((rc = upload(ctx, ctx->in1, points_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if (points_inf && (rc = upload(ctx, ctx->in2, points_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, 16)) != ECGPU_OK) return rc;
-    if ((rc = ecgpu_point_sum_dev(ctx, curve, ctx->in1.p, points_inf ? ctx->in2.p : nullptr, n, ctx->out0.p,
-                                  ctx->out1.p)) != ECGPU_OK)
-        return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, 1);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(!out_xy || (n && !points_xy))) return h.rc;
+    return staged(ctx, n, {{points_xy, &ctx->in1, 2 * h.L}, {points_inf, &ctx->in2, 1}}, {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return ecgpu_point_sum_dev(ctx, curve, in[0], in[1], m, out[0], out[1]); }, STAGE_REDUCE);
 }
 
+// (the three below launch their kernel themselves, as the device call of `staged`)
 int ecgpu_k256_glv_decompose(ecgpu_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* r1, uint8_t* r2) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    if (n && (!scalars || !r1 || !r2)) return arg_error(ctx, __func__);
+    HostCall h(ctx, __func__, ECGPU_K256);
+    if (h.bad(n && (!scalars || !r1 || !r2))) return h.rc;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, scalars, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->in1, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    launch_k256_glv(ctx->stream, (const uint8_t*)ctx->in0.p, n, (uint8_t*)ctx->out0.p, (uint8_t*)ctx->in1.p, ctx->d_status);
-    if ((rc = finish(ctx)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, r1, ctx->out0, n * 32)) != ECGPU_OK) return rc;
-    return download(ctx, r2, ctx->in1, n * 32);
+    return staged(ctx, n, {{scalars, &ctx->in0, 32}}, {{r1, &ctx->out0, 32}, {r2, &ctx->in1, 32}}, [&](auto in, auto out, size_t m) {
+        int rc = reset_status(ctx);
+        if (rc != ECGPU_OK) return rc;
+        launch_k256_glv(ctx->stream, (const uint8_t*)in[0], m, (uint8_t*)out[0], (uint8_t*)out[1], ctx->d_status);
+        return finish(ctx);
+    }, STAGE_WHOLE);
 }
 
 int ecgpu_selftest_field(ecgpu_ctx* ctx, int curve, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!a || !out)) return arg_error(ctx, __func__);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!a || !out))) return h.rc;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, a, n * L)) != ECGPU_OK) return rc;
-    if (b && (rc = upload(ctx, ctx->in1, b, n * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    rc = dispatch(curve, [&](auto c) {
-        launch_selftest_field<decltype(c)>(ctx->stream, op, (const uint8_t*)ctx->in0.p, b ? (const uint8_t*)ctx->in1.p : nullptr, n,
-                                           (uint8_t*)ctx->out0.p, ctx->d_status);
-        return (int)ECGPU_OK;
-    });
-    if (rc != ECGPU_OK) return rc;
-    if ((rc = finish(ctx)) != ECGPU_OK) return rc;
-    return download(ctx, out, ctx->out0, n * L);
+    return staged(ctx, n, {{a, &ctx->in0, h.L}, {b, &ctx->in1, h.L}}, {{out, &ctx->out0, h.L}}, [&](auto in, auto o, size_t m) {
+        int rc = reset_status(ctx);
+        if (rc != ECGPU_OK) return rc;
+        rc = dispatch(curve, [&](auto c) {
+            launch_selftest_field<decltype(c)>(ctx->stream, op, (const uint8_t*)in[0], (const uint8_t*)in[1], m, (uint8_t*)o[0], ctx->d_status);
+            return (int)ECGPU_OK;
+        });
+        return rc != ECGPU_OK ? rc : finish(ctx);
+    }, STAGE_WHOLE);
 }
 
 int ecgpu_selftest_point(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p_xy, const uint8_t* p_inf, const uint8_t* q_xy,
                          const uint8_t* q_inf, size_t n, uint8_t* out_xy, uint8_t* out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    SyncScope sync_scope(ctx);
-    if (sync_scope.rc != ECGPU_OK) return sync_scope.rc;
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
-    if (n && (!p_xy || !out_xy || !out_inf)) return arg_error(ctx, __func__);
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!p_xy || !out_xy || !out_inf))) return h.rc;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = upload(ctx, ctx->in0, p_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if (p_inf && (rc = upload(ctx, ctx->in2, p_inf, n)) != ECGPU_OK) return rc;
-    if (q_xy && (rc = upload(ctx, ctx->in1, q_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if (q_inf && (rc = upload(ctx, ctx->in3, q_inf, n)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out0, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->out1, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    rc = dispatch(curve, [&](auto c) {
-        launch_selftest_point<decltype(c)>(ctx->stream, op, (const uint8_t*)ctx->in0.p, p_inf ? (const uint8_t*)ctx->in2.p : nullptr,
-                                           q_xy ? (const uint8_t*)ctx->in1.p : nullptr, q_inf ? (const uint8_t*)ctx->in3.p : nullptr, n,
-                                           (uint8_t*)ctx->out0.p, (uint8_t*)ctx->out1.p, ctx->d_status);
-        return (int)ECGPU_OK;
-    });
-    if (rc != ECGPU_OK) return rc;
-    if ((rc = finish(ctx)) != ECGPU_OK) return rc;
-    if ((rc = download(ctx, out_xy, ctx->out0, n * 2 * L)) != ECGPU_OK) return rc;
-    return download(ctx, out_inf, ctx->out1, n);
+    return staged(ctx, n, {{p_xy, &ctx->in0, 2 * h.L}, {p_inf, &ctx->in2, 1}, {q_xy, &ctx->in1, 2 * h.L}, {q_inf, &ctx->in3, 1}},
+                  {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}}, [&](auto in, auto o, size_t m) {
+                      int rc = reset_status(ctx);
+                      if (rc != ECGPU_OK) return rc;
+                      rc = dispatch(curve, [&](auto c) {
+                          launch_selftest_point<decltype(c)>(ctx->stream, op, (const uint8_t*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2],
+                                                             (const uint8_t*)in[3], m, (uint8_t*)o[0], (uint8_t*)o[1], ctx->d_status);
+                          return (int)ECGPU_OK;
+                      });
+                      return rc != ECGPU_OK ? rc : finish(ctx);
+                  }, STAGE_WHOLE);
 }
 
 int ecgpu_valu_probe(ecgpu_ctx* ctx, int which, double* ops_per_sec) {
