@@ -157,7 +157,8 @@ template <> void launch_sm2dsa_finish<CurveT>(hipStream_t s, const uint8_t* e, c
 }
 template <> void launch_selftest_field<CurveT>(hipStream_t s, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out,
                                                int* status) {
-    hipLaunchKernelGGL(k_selftest_field<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, op, a, b, n, out, status);
+    if (op >= 30) hipLaunchKernelGGL(k_selftest_field_raw<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, op, a, b, n, out, status);
+    else hipLaunchKernelGGL(k_selftest_field<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, op, a, b, n, out, status);
 }
 template <> void launch_selftest_point<CurveT>(hipStream_t s, int op, const uint8_t* pxy, const uint8_t* pinf, const uint8_t* qxy,
                                                const uint8_t* qinf, size_t n, uint8_t* out_xy, uint8_t* out_inf, int* status) {

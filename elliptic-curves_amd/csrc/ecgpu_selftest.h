@@ -8,6 +8,7 @@
 
 #include "ecgpu_kernels.h"
 #include "ecgpu_rows.h"
+#include "ecgpu_selftest_raw.h"
 
 namespace ecgpu {
 
@@ -144,6 +145,34 @@ __global__ void __launch_bounds__(BLOCK) k_selftest_field(int op, const uint8_t*
         break;
     case 21: F::to_canonical(wr, x); break;    // internal-domain round trip
     default:
+#pragma unroll
+        for (int t = 0; t < N; t++) wr[t] = 0;
+        atomicOr(status, ST_BAD_SCALAR);
+    }
+    store_wire<C>(out + i * WB, wr);
+}
+
+// field, raw domain, and scalars mod n (ecgpu_selftest_raw.h; ecgpu_selftest_field sends every op >= 30 here): 30 - 39 the field
+// operations at the magnitude limits of the parameter set, on operands that enter through F::unpack — limbs as the caller wrote
+// them, values in [p, 2p) included, so NO canonical check — and 40 - 44 ScalarN<C> (a * b, 1 / a, reduce_wire, is_high, to_mont ->
+// from_mont), whose operands are below n or, for reduce_wire, any wire value.  A kernel of its own, so that the code object of
+// k_selftest_field stays what it was.  It contains the k256 assembly blocks: 128 VGPRs or more (ecgpu_field.h), which
+// __launch_bounds__(BLOCK) grants.
+template <class C>
+__global__ void __launch_bounds__(BLOCK) k_selftest_field_raw(int op, const uint8_t* __restrict__ a, const uint8_t* __restrict__ b, size_t n,
+                                                              uint8_t* __restrict__ out, int* status) {
+    constexpr int N = C::N, WB = WireBytes<C>::value;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wa[N], wb[N], wr[N];
+    load_wire<C>(wa, a + i * WB);
+    if (b) load_wire<C>(wb, b + i * WB);
+    else {
+#pragma unroll
+        for (int t = 0; t < N; t++) wb[t] = 0;
+    }
+    const bool known = op >= 40 ? selftest_scalar<C>(op - 40, wa, wb, wr) : selftest_field_raw<C>(op, wa, wb, wr);
+    if (!known) {
 #pragma unroll
         for (int t = 0; t < N; t++) wr[t] = 0;
         atomicOr(status, ST_BAD_SCALAR);

@@ -635,11 +635,19 @@ int ecgpu_batch_decompress_dev(ecgpu_ctx *ctx, int curve, const void *d_xs, cons
  *   multiplication of the MSM's Horner chain: 13 a b of lane (i mod 4) of the wave in every lane i, 17 1/a by the variable-time
  *   division steps.  The reference's counterparts: `FieldElement::{add, sub, mul, square, invert,
  *   negate, double, sqrt}` (k256/src/arithmetic/field.rs, p256/src/arithmetic/field.rs, primefield/src/monty.rs).
+ *   Ops 30 - 44 take operands as they are, NOT only canonical ones (a kernel of their own; csrc/ecgpu_selftest_raw.h).  30 - 39, the
+ *   raw domain: a, b enter the internal domain as written (Field::unpack: limbs of all ones, values in [p, 2p) below 2^(8 L)) and
+ *   are scaled by repeated addition to the magnitude limits of the parameter set; the result is the internal-domain value in
+ *   [0, p).  With MP = MAXPROD, A1 = min(MP, MAXMAG), B1 = MP / A1, A2 = 5 / 4 / 3 / 2 for MP >= 25 / 16 / 9 / else, B2 = MP / A2,
+ *   SQ = SQLIM: 30 mul(A1 a, B1 b), 31 mul(A2 a, B2 b), 32 sqr(SQ a), 33 mul(a, b), 34 the fused mul_sub(A2 a, B2 b, 6 b) and
+ *   35 sqr_sub(SQ a, 6 b) of every parameter set, 36 mul2(A2 a, floor(B2 / 2) b, A2 b, ceil(B2 / 2) a), 37 3 a - 3 b (k256) or
+ *   6 a - 6 b, 38 to_canonical(a), 39 is_zero(a) as 0 / 1.  40 - 44, scalars modulo the group order (a, b < n): 40 a * b,
+ *   41 1 / a (0 for 0), 42 reduce_wire(a) for any a < 2^(8 L), 43 is_high(a) as 0 / 1, 44 a through to_mont and from_mont.
  * ecgpu_selftest_point: out[i] = op(P[i], Q[i]); op 0 P + Q (complete), 1 the same mixed, 2 2P, 3 -P, 4 P - Q, 5 the same
  *   mixed, and the incomplete formulas inside their domain (P, Q finite, P != +-Q): 6 2P (Jacobian), 7 2P + Q (Jacobian
  *   doubling + mixed addition), 8 P + Q (XYZZ mixed), 9 P + Q (XYZZ affine + affine), 10 (k256; n a multiple of 64) 32 P of
  *   the wave's FIRST point in every lane, by five row-parallel complete doublings.
- * ECGPU_ERR_POINT: an input >= p / off the curve; ECGPU_ERR_SCALAR_RANGE: unknown op. */
+ * ECGPU_ERR_POINT: an input >= p (field ops 0 - 21) / off the curve; ECGPU_ERR_SCALAR_RANGE: unknown op. */
 int ecgpu_selftest_field(ecgpu_ctx *ctx, int curve, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
 int ecgpu_selftest_point(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p_xy, const uint8_t *p_inf, const uint8_t *q_xy,
                          const uint8_t *q_inf, size_t n, uint8_t *out_xy, uint8_t *out_inf);

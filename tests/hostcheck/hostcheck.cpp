@@ -19,6 +19,7 @@
 #include "../../elliptic-curves_amd/csrc/ecgpu_sm3.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_belt.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_verify.h"
+#include "../../elliptic-curves_amd/csrc/ecgpu_selftest_raw.h"
 
 using namespace ecgpu;
 
@@ -60,9 +61,23 @@ typename Field<C>::M1 times21(const typename Field<C>::M1& y) {
     }
 }
 
+// ops 30 - 39: the raw-domain operations of ecgpu_selftest_raw.h (operands through F::unpack, no canonical check; what the
+// device runs as k_selftest_field_raw)
+template <class C>
+int field_raw_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
+    uint32_t wa[C::N], wb[C::N], wr[C::N];
+    load_be_wire<C>(wa, a);
+    for (int i = 0; i < C::N; i++) wb[i] = 0;
+    if (b) load_be_wire<C>(wb, b);
+    if (!selftest_field_raw<C>(op, wa, wb, wr)) return -1;
+    store_be_wire<C>(out, wr);
+    return 0;
+}
+
 template <class C>
 int field_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     using F = Field<C>;
+    if (op >= 30) return field_raw_op<C>(op, a, b, out);
     bool ok;
     auto x = F::from_bytes(a, &ok);
     if (!ok) return -3;
@@ -742,23 +757,37 @@ int decompress(const uint8_t* xs, const uint8_t* odd, size_t n, uint8_t* out_xy,
     return 0;
 }
 
-// ScalarN<C>: op 0 a*b mod n, 1 1/a mod n, 2 a mod n (a < 2^(32N)), 3 is_high(a) -> out[last byte]
+// ScalarN<C>: op 0 a*b mod n, 1 1/a mod n, 2 a mod n (a < 2^(32N)), 3 is_high(a) -> out[last byte], 4 to_mont -> from_mont
+// (ecgpu_selftest_raw.h: the device runs the same function as ops 40 - 44 of its field self-test)
 template <class C>
 int scalar_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
-    using S = ScalarN<C>;
     constexpr int N = C::N;
     uint32_t x[N], y[N], r[N];
     load_be_wire<C>(x, a);
-    for (int i = 0; i < N; i++) r[i] = 0;
+    for (int i = 0; i < N; i++) y[i] = 0;
     if (b) load_be_wire<C>(y, b);
-    switch (op) {
-    case 0: S::mul(r, x, y); break;
-    case 1: S::inv(r, x); break;
-    case 2: S::reduce_wire(r, x); break;
-    case 3: r[0] = S::is_high(x) ? 1u : 0u; break;
-    default: return -1;
-    }
+    if (!selftest_scalar<C>(op, x, y, r)) return -1;
     store_be_wire<C>(out, r);
+    return 0;
+}
+
+// n records per call (b may be null): what a test with thousands of vectors uses instead of one ctypes call each
+template <class C>
+int field_op_batch(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    constexpr size_t WB = WireBytes<C>::value;
+    for (size_t i = 0; i < n; i++) {
+        const int rc = field_op<C>(op, a + i * WB, b ? b + i * WB : nullptr, out + i * WB);
+        if (rc != 0) return rc;
+    }
+    return 0;
+}
+template <class C>
+int scalar_op_batch(int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    constexpr size_t WB = WireBytes<C>::value;
+    for (size_t i = 0; i < n; i++) {
+        const int rc = scalar_op<C>(op, a + i * WB, b ? b + i * WB : nullptr, out + i * WB);
+        if (rc != 0) return rc;
+    }
     return 0;
 }
 
@@ -798,6 +827,12 @@ int hc_bip340_challenge(const uint8_t* r, const uint8_t* pk, const uint8_t* m, s
 }
 int hc_scalar_op(int curve, int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     DISPATCH(curve, scalar_op, (op, a, b, out))
+}
+int hc_field_op_batch(int curve, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    DISPATCH(curve, field_op_batch, (op, a, b, n, out))
+}
+int hc_scalar_op_batch(int curve, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    DISPATCH(curve, scalar_op_batch, (op, a, b, n, out))
 }
 int hc_field_chain(int curve, const uint8_t* a, const uint8_t* b, int steps, uint8_t* out) {
     DISPATCH(curve, field_chain, (a, b, steps, out))

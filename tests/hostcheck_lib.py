@@ -17,7 +17,7 @@ _lib = None
 
 def build():
     import fcntl
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_selftest_raw.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
 
     def fresh():
         return os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps)
@@ -75,6 +75,25 @@ def scalar_op(curve, op, a, b=None):
     A, B = _a(a), _a(b)
     assert lib().hc_scalar_op(curve, op, _p(A), _p(B), _p(out)) == 0
     return bytes(out)
+
+
+def field_op_batch(curve, op, a, b=None):
+    """field_op on n = len(a) / L records in one call; the n results as one bytes object."""
+    A, B = _a(a), _a(b)
+    n = A.size // L[curve]
+    out = np.zeros(max(n, 1) * L[curve], np.uint8)
+    rc = lib().hc_field_op_batch(curve, op, _p(A), _p(B), ctypes.c_size_t(n), _p(out))
+    assert rc == 0, rc
+    return bytes(out[: n * L[curve]])
+
+
+def scalar_op_batch(curve, op, a, b=None):
+    A, B = _a(a), _a(b)
+    n = A.size // L[curve]
+    out = np.zeros(max(n, 1) * L[curve], np.uint8)
+    rc = lib().hc_scalar_op_batch(curve, op, _p(A), _p(B), ctypes.c_size_t(n), _p(out))
+    assert rc == 0, rc
+    return bytes(out[: n * L[curve]])
 
 
 def field_chain(curve, a, b, steps):

@@ -1686,7 +1686,7 @@ def test_msm_fused_tail_form(eng, keng, curve, monkeypatch):
         assert bytes(got) == bytes(o) and gf == int(oi[0]), (curve, case)
 
 
-@pytest.mark.parametrize("curve", ["k256", "p256", "p384"])
+@pytest.mark.parametrize("curve", [c for c in ALL_CURVES if c != "sm2"])          # every parameter set with ECDSA: every ScalarN instantiation
 def test_signature_batches_share_their_scalar_inversions(eng, curve):
     """ECDSA verification and public-key recovery invert one scalar per signature modulo the group order (`Scalar::invert`,
     k256/src/arithmetic/scalar.rs:139-143); k_scalar_batch_inv does it for the whole batch by Montgomery's trick, several signatures per
