@@ -65,6 +65,8 @@ ABI_SYMBOLS = [
     "ecgpu_batch_mul_ct_xyz", "ecgpu_batch_mul_ct_xyz_dev", "ecgpu_lincomb_ct_xyz", "ecgpu_lincomb_ct_xyz_dev",
     "ecgpu_batch_mul_xyz", "ecgpu_batch_mul_xyz_dev", "ecgpu_msm_xyz", "ecgpu_msm_xyz_dev", "ecgpu_batch_mul_base_and_mul_add_xyz",
     "ecgpu_batch_mul_base_and_mul_add_xyz_dev", "ecgpu_msm_parts_xyz_dev", "ecgpu_group_msm_xyz", "ecgpu_group_msm_xyz_dev",
+    "ecgpu_ecdsa_sign_batch", "ecgpu_ecdsa_sign_batch_dev", "ecgpu_ecdsa_sign_rfc6979_batch", "ecgpu_ecdsa_sign_rfc6979_batch_dev",
+    "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_sign_msg_batch_dev", "ecgpu_schnorr_sign_raw_batch", "ecgpu_schnorr_sign_raw_batch_dev",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -616,6 +618,75 @@ class Engine:
     def schnorr_verify_raw_dev(self, d_pk_x, d_msgs, msg_len, d_sigs, n, d_ok):
         self._chk(self._lib.ecgpu_schnorr_verify_raw_batch_dev(self._ctx, _dp(d_pk_x), _dp(d_msgs) if msg_len else None,
                                                                ctypes.c_size_t(msg_len), _dp(d_sigs), ctypes.c_size_t(n), _dp(d_ok)))
+
+    # ---- signing (secret keys and nonces: the uniform-schedule generator multiplication, scratch wiped behind each call) ----
+    def _sign_out(self, n, L):
+        return np.zeros(n * 2 * L, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+    def ecdsa_sign(self, curve, d, k, z, normalize_s=False):
+        """ECDSA with the caller's nonce (the hazmat form): d, k, z n*L big-endian bytes each; returns (sig uint8[n*2L] = r || s,
+        recid uint8[n] as ecdsa_recover takes it, ok uint8[n]).  normalize_s: the curve's NORMALIZE_S (True for k256)."""
+        L = _field_bytes(curve)
+        dd, kk, zz = _host(d), _host(k), _host(z)
+        n = dd.size // L
+        _need("d", dd, n * L); _need("k", kk, n * L); _need("z", zz, n * L)
+        sig, recid, ok = self._sign_out(n, L)
+        self._chk(self._lib.ecgpu_ecdsa_sign_batch(self._ctx, curve, _hp(dd), _hp(kk), _hp(zz), ctypes.c_size_t(n),
+                                                   int(bool(normalize_s)), _hp(sig), _hp(recid), _hp(ok)))
+        return sig, recid, ok
+
+    def ecdsa_sign_dev(self, curve, d_d, d_k, d_z, n, normalize_s, d_out_sig, d_out_recid, d_ok):
+        self._chk(self._lib.ecgpu_ecdsa_sign_batch_dev(self._ctx, curve, _dp(d_d), _dp(d_k), _dp(d_z), ctypes.c_size_t(n),
+                                                       int(bool(normalize_s)), _dp(d_out_sig), _dp(d_out_recid), _dp(d_ok)))
+
+    def ecdsa_sign_rfc6979(self, curve, d, z, normalize_s=False):
+        """`PrehashSigner::sign_prehash`: the nonce of RFC 6979 generated on the device; d, z n*L bytes; returns (sig, recid, ok)."""
+        L = _field_bytes(curve)
+        dd, zz = _host(d), _host(z)
+        n = dd.size // L
+        _need("d", dd, n * L); _need("z", zz, n * L)
+        sig, recid, ok = self._sign_out(n, L)
+        self._chk(self._lib.ecgpu_ecdsa_sign_rfc6979_batch(self._ctx, curve, _hp(dd), _hp(zz), ctypes.c_size_t(n),
+                                                           int(bool(normalize_s)), _hp(sig), _hp(recid), _hp(ok)))
+        return sig, recid, ok
+
+    def ecdsa_sign_rfc6979_dev(self, curve, d_d, d_z, n, normalize_s, d_out_sig, d_out_recid, d_ok):
+        self._chk(self._lib.ecgpu_ecdsa_sign_rfc6979_batch_dev(self._ctx, curve, _dp(d_d), _dp(d_z), ctypes.c_size_t(n),
+                                                               int(bool(normalize_s)), _dp(d_out_sig), _dp(d_out_recid), _dp(d_ok)))
+
+    def ecdsa_sign_msg(self, curve, d, msgs, msg_len, normalize_s=False):
+        """`Signer::sign(msg)`: keys n*L, messages n*msg_len (one length per call, 0 allowed); the curve's digest, bits2field and the
+        RFC 6979 nonce run on the device; returns (sig, recid, ok)."""
+        L = _field_bytes(curve)
+        dd = _host(d)
+        mm = _host(msgs) if msg_len else None
+        n = dd.size // L
+        _need("d", dd, n * L); _need("msgs", mm, n * msg_len)
+        sig, recid, ok = self._sign_out(n, L)
+        self._chk(self._lib.ecgpu_ecdsa_sign_msg_batch(self._ctx, curve, _hp(dd), _hp(mm), ctypes.c_size_t(msg_len), ctypes.c_size_t(n),
+                                                       int(bool(normalize_s)), _hp(sig), _hp(recid), _hp(ok)))
+        return sig, recid, ok
+
+    def ecdsa_sign_msg_dev(self, curve, d_d, d_msgs, msg_len, n, normalize_s, d_out_sig, d_out_recid, d_ok):
+        self._chk(self._lib.ecgpu_ecdsa_sign_msg_batch_dev(self._ctx, curve, _dp(d_d), _dp(d_msgs) if msg_len else None,
+                                                           ctypes.c_size_t(msg_len), ctypes.c_size_t(n), int(bool(normalize_s)),
+                                                           _dp(d_out_sig), _dp(d_out_recid), _dp(d_ok)))
+
+    def schnorr_sign_raw(self, sk, msgs, msg_len, aux_rand):
+        """BIP340 `sign_raw` (k256): keys n*32, messages n*msg_len, aux_rand n*32; returns (sig uint8[n*64] = x(R) || s, ok uint8[n])."""
+        kk, aa = _host(sk), _host(aux_rand)
+        mm = _host(msgs) if msg_len else None
+        n = kk.size // 32
+        _need("sk", kk, n * 32); _need("aux_rand", aa, n * 32); _need("msgs", mm, n * msg_len)
+        sig, ok = np.zeros(n * 64, np.uint8), np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_schnorr_sign_raw_batch(self._ctx, _hp(kk), _hp(mm), ctypes.c_size_t(msg_len), _hp(aa),
+                                                         ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
+
+    def schnorr_sign_raw_dev(self, d_sk, d_msgs, msg_len, d_aux_rand, n, d_out_sig, d_ok):
+        self._chk(self._lib.ecgpu_schnorr_sign_raw_batch_dev(self._ctx, _dp(d_sk), _dp(d_msgs) if msg_len else None,
+                                                             ctypes.c_size_t(msg_len), _dp(d_aux_rand), ctypes.c_size_t(n),
+                                                             _dp(d_out_sig), _dp(d_ok)))
 
     def decompress(self, curve, xs, y_is_odd):
         """DecompressPoint::decompress for a batch: returns (xy uint8[n*2L], ok uint8[n])."""

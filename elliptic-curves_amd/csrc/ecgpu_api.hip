@@ -102,6 +102,11 @@ struct ecgpu_ctx {
     DevBuf ec_u1, ec_u2, ec_q, ec_valid, ec_xy, ec_inf, ec_r, ec_e, ec_s, ec_id;   // signature verification scratch
     DevBuf ec_winv;                    // the batch's s^-1 / r^-1 modulo the group order (k_scalar_batch_inv; its prefix products use `prefix`)
     DevBuf ct_flags;             // one verdict byte per element of a uniform-schedule batch
+    DevBuf sg_k, sg_flag, sg_state, sg_dp;   // signing: the nonces handed to k_fixed_base_ct, their verdicts, the RFC 6979 generator's
+                                 // K / V state between its two kernels, the fixed-up Schnorr key d' || x(P) — all wiped behind the call
+    DevBuf out2;                 // a third staged output (the recovery ids of the host-pointer signing calls)
+    int rfc6979_cap = 128;       // candidates the RFC 6979 generator tries per element; lowered by the tests only
+                                 // (ecgpu_testhook_rfc6979_max_candidates, this context alone)
     DevBuf cx_xy, cx_inf;        // x || y + flag records decoded from compressed input (ecgpu_msm_compressed, ecgpu_batch_mul_compressed)
                                  // or converted from projective input (the variable-time _xyz forms; their product chain uses `prefix`)
     bool keep_status = false;    // the status word already holds the verdicts of a first stage of the call: do not clear it
@@ -268,7 +273,7 @@ struct SyncScope {
 // from its secrets — k P in projective form, the running products of the batch inversion, the affine products of an ECDH —
 // is zeroed behind its last kernel (stream-ordered), and `staging` also clears the copies a host-pointer call made of the
 // caller's scalars and results.  The caller's own buffers are the caller's to wipe; ecgpu_wipe does the same on request.
-enum : int { WIPE_SCRATCH = 1, WIPE_EC = 2, WIPE_STAGING = 4 };
+enum : int { WIPE_SCRATCH = 1, WIPE_EC = 2, WIPE_STAGING = 4, WIPE_SIGN = 8 };
 void wipe_bufs(ecgpu_ctx* ctx, std::initializer_list<DevBuf*> bufs) {
     // what has been asked of a buffer since its last wipe, not its capacity: after one 2^20-term batch the scratch holds
     // ~170 MB, and zeroing all of it behind every later 1,024-scalar `_ct` call (or every chunk of a pipelined one) cost tens
@@ -282,6 +287,7 @@ void wipe_scratch(ecgpu_ctx* ctx, int what) {
     if (what & WIPE_SCRATCH) wipe_bufs(ctx, {&ctx->proj, &ctx->prefix});
     if (what & WIPE_EC) wipe_bufs(ctx, {&ctx->ec_xy, &ctx->ec_inf});
     if (what & WIPE_STAGING) wipe_bufs(ctx, {&ctx->in0, &ctx->in3, &ctx->out0, &ctx->out1});
+    if (what & WIPE_SIGN) wipe_bufs(ctx, {&ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp, &ctx->ct_flags});
 }
 struct CtWipe {
     ecgpu_ctx* ctx;
@@ -659,6 +665,51 @@ int mul_base_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out
                             (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     record(ctx, 1);
     if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
+    record(ctx, 2);
+    rc = finish(ctx);
+    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
+    return rc;
+}
+
+// ---- signing (ecgpu_sign.h): nonce -> k G on the uniform-schedule fixed-base kernel -> affine R -> the finish kernel ------------
+// Everything between the caller's arrays lives in context scratch that CtWipe zeroes behind the last kernel, whatever way the call
+// leaves.  d_k == nullptr: the nonce of RFC 6979 (k_rfc6979_first, k_rfc6979_retry).  from_msg: d_z holds n messages of msg_len
+// bytes instead of prehashes; z = bits2field(digest) goes to ec_e first (k_sign_hash_msg, inside the call's timed span).
+template <class C>
+int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_z, size_t n, int normalize_s, void* d_sig,
+                   void* d_recid, void* d_ok, bool from_msg = false, size_t msg_len = 0) {
+    constexpr int NS = Field<C>::NS;
+    constexpr size_t L = WireBytes<C>::value;
+    int rc;
+    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    CtWipe wipe(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN);
+    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sg_k, n * L + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sg_flag, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ec_xy, n * 2 * L + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
+    if (!d_k && (rc = ensure(ctx, ctx->sg_state, n * rfc6979_state_bytes<C>() + 16)) != ECGPU_OK) return rc;
+    if (from_msg && (rc = ensure(ctx, ctx->ec_e, n * L + 16)) != ECGPU_OK) return rc;
+    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    record(ctx, 0);
+    if (from_msg) {
+        launch_sign_hash_msg<C>(ctx->stream, (const uint8_t*)d_z, msg_len, n, (uint8_t*)ctx->ec_e.p);
+        d_z = ctx->ec_e.p;
+    }
+    if (d_k)
+        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, (uint8_t*)ctx->sg_k.p, (uint8_t*)ctx->sg_flag.p);
+    else
+        launch_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_z, n, ctx->rfc6979_cap, (uint8_t*)ctx->sg_k.p,
+                          (uint8_t*)ctx->sg_flag.p, ctx->sg_state.p);
+    launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)ctx->sg_k.p, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
+                            (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    record(ctx, 1);
+    if ((rc = normalize_out<C>(ctx, n, ctx->ec_xy.p, ctx->ec_inf.p)) != ECGPU_OK) return rc;
+    launch_ecdsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)ctx->sg_k.p, (const uint8_t*)ctx->sg_flag.p,
+                                (const uint8_t*)d_z, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, n, normalize_s,
+                                (uint8_t*)d_sig, (uint8_t*)d_recid, (uint8_t*)d_ok);
     record(ctx, 2);
     rc = finish(ctx);
     collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
@@ -1504,7 +1555,7 @@ void ecgpu_destroy(ecgpu_ctx* ctx) {
                       &ctx->out0, &ctx->out1, &ctx->msm_ws, &ctx->ec_u1, &ctx->ec_u2, &ctx->ec_winv, &ctx->ec_q, &ctx->ec_valid, &ctx->ec_xy,
                       &ctx->ec_inf, &ctx->ec_r, &ctx->ec_e, &ctx->ec_s, &ctx->ec_id})
         if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : {&ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf})
+    for (DevBuf* b : {&ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp, &ctx->out2})
         if (b->p) (void)hipFree(b->p);
     for (auto& l : ctx->lane) {
         if (l.s) (void)hipStreamSynchronize(l.s);
@@ -1701,13 +1752,20 @@ int ecgpu_wipe(ecgpu_ctx* ctx) {
         if (l.s) HIP_TRY(ctx, hipStreamSynchronize(l.s));
     for (DevBuf* b : {&ctx->proj, &ctx->prefix, &ctx->vtab, &ctx->bases, &ctx->in0, &ctx->in1, &ctx->in2, &ctx->in3, &ctx->out0, &ctx->out1,
                       &ctx->msm_ws, &ctx->ec_u1, &ctx->ec_u2, &ctx->ec_winv, &ctx->ec_q, &ctx->ec_valid, &ctx->ec_xy, &ctx->ec_inf, &ctx->ec_r, &ctx->ec_e,
-                      &ctx->ec_s, &ctx->ec_id, &ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf})
+                      &ctx->ec_s, &ctx->ec_id, &ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp,
+                      &ctx->out2})
         if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     for (auto& l : ctx->lane)
         for (DevBuf* b : {&l.ws, &l.proj, &l.prefix, &l.cx_xy, &l.cx_inf})
             if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return ECGPU_OK;
+}
+
+// test-only (not in include/ecgpu.h): the candidate cap of the RFC 6979 generator of THIS context; anything outside [1, 128]
+// restores 128
+void ecgpu_testhook_rfc6979_max_candidates(ecgpu_ctx* ctx, int cap) {
+    if (ctx) ctx->rfc6979_cap = cap >= 1 && cap <= 128 ? cap : 128;
 }
 
 // test-only (not in include/ecgpu.h): comb tables above `mb` MiB are refused as if the allocation had failed; 0 switches it off
@@ -2083,6 +2141,80 @@ int ecgpu_schnorr_verify_raw_batch_dev(ecgpu_ctx* ctx, const void* d_pk_x, const
     return verify_dev<K256Params>(ctx, VERIFY_SCHNORR_RAW, d_msgs, nullptr, d_sigs, d_pk_x, n, 0, d_ok, msg_len);
 }
 
+// ---- signing (ecgpu_sign.h): the entry points around ecdsa_sign_dev ----
+// every argument is checked before anything is queued.  from_msg: d_z is the message array (NULL allowed when msg_len == 0)
+static int ecdsa_sign_entry(ecgpu_ctx* ctx, const char* fn, int curve, bool rfc6979, const void* d_d, const void* d_k, const void* d_z,
+                            size_t n, int normalize_s, void* d_sig, void* d_recid, void* d_ok, bool from_msg = false, size_t msg_len = 0) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    const bool z_bad = from_msg ? (msg_len && !d_z) : (!d_z || !aligned16(d_z));
+    if (n && (!d_d || (!rfc6979 && !d_k) || z_bad || !d_sig || !d_recid || !d_ok || !aligned16(d_d) || (d_k && !aligned16(d_k)) ||
+              !aligned16(d_sig)))
+        return arg_error(ctx, fn);
+    if (curve == ECGPU_SM2 || curve == ECGPU_BIGN256 || (rfc6979 && curve == ECGPU_P192))   // not ECDSA; p192 has no `DigestAlgorithm`
+        return curve_error(ctx, fn);
+    const int rc = dispatch(curve, [&](auto c) {
+        return ecdsa_sign_dev<decltype(c)>(ctx, d_d, rfc6979 ? nullptr : d_k, d_z, n, normalize_s, d_sig, d_recid, d_ok, from_msg, msg_len);
+    });
+    return rc == ECGPU_ERR_CURVE ? curve_error(ctx, fn) : rc;
+}
+
+int ecgpu_ecdsa_sign_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_d, const void* d_k, const void* d_z, size_t n, int normalize_s,
+                               void* d_out_sig, void* d_out_recid, void* d_ok) {
+    // `hazmat::sign_prehashed` with the caller's nonce: R = k G, r = x(R) mod n, s = (z + r d) / k.  See ecgpu_sign.h.
+    return ecdsa_sign_entry(ctx, __func__, curve, false, d_d, d_k, d_z, n, normalize_s, d_out_sig, d_out_recid, d_ok);
+}
+
+int ecgpu_ecdsa_sign_rfc6979_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_d, const void* d_z, size_t n, int normalize_s,
+                                       void* d_out_sig, void* d_out_recid, void* d_ok) {
+    // `PrehashSigner::sign_prehash`: the nonce of RFC 6979 section 3.2 from the device's HMAC-DRBG.  See ecgpu_sign.h.
+    return ecdsa_sign_entry(ctx, __func__, curve, true, d_d, nullptr, d_z, n, normalize_s, d_out_sig, d_out_recid, d_ok);
+}
+
+int ecgpu_ecdsa_sign_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_d, const void* d_msgs, size_t msg_len, size_t n,
+                                   int normalize_s, void* d_out_sig, void* d_out_recid, void* d_ok) {
+    // `Signer::sign(msg)`: the curve's digest on the device, z = bits2field(digest), then the RFC 6979 form.  See ecgpu_sign.h.
+    return ecdsa_sign_entry(ctx, __func__, curve, true, d_d, nullptr, d_msgs, n, normalize_s, d_out_sig, d_out_recid, d_ok, true, msg_len);
+}
+
+int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_t msg_len, const void* d_aux_rand,
+                                     size_t n, void* d_out_sig, void* d_ok) {
+    // `SigningKey::sign_raw(msg, aux_rand)` with the key fix-up: P = d G, the nonce hashes, R = k G, s = k + e d.  See ecgpu_sign.h.
+    using C = K256Params;
+    constexpr int NS = Field<C>::NS;
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    if (n && (!d_sk || !d_aux_rand || !d_out_sig || !d_ok || (msg_len && !d_msgs) || !aligned16(d_sk) || !aligned16(d_aux_rand) ||
+              !aligned16(d_out_sig)))
+        return arg_error(ctx, __func__);
+    int rc;
+    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    CtWipe wipe(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN);
+    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sg_k, n * 32 + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sg_flag, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->sg_dp, n * 64 + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ec_xy, n * 64 + 16)) != ECGPU_OK) return rc;
+    if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
+    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *dp = (uint8_t*)ctx->sg_dp.p;
+    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
+    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
+    record(ctx, 0);
+    launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_sk, n, k, flag);                   // d, or 1 in place of an unusable key
+    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // P = d G
+    launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n, dp, k, flag);
+    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    record(ctx, 1);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
+    launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
+    record(ctx, 2);
+    rc = finish(ctx);
+    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
+    return rc;
+}
+
 static int ecdh_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, size_t n, void* d_out_x, void* d_ok,
                     bool ct) {
     // SharedSecret_i = x(k_i * P_i): the variable-base kernel (ct: its uniform-schedule form), normalisation into scratch,
@@ -2364,6 +2496,47 @@ int ecgpu_schnorr_verify_raw_batch(ecgpu_ctx* ctx, const uint8_t* pk_x, const ui
     return staged(ctx, n, {{pk_x, &ctx->in0, 32}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {sigs, &ctx->in3, 64}},
                   {{ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
                       return ecgpu_schnorr_verify_raw_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0]);
+                  });
+}
+
+// ---- signing: keys, nonces and aux_rand are staged as secrets (zeroed behind the call); signatures are public ----
+int ecgpu_ecdsa_sign_batch(ecgpu_ctx* ctx, int curve, const uint8_t* d, const uint8_t* k, const uint8_t* z, size_t n, int normalize_s,
+                           uint8_t* out_sig, uint8_t* out_recid, uint8_t* ok) {
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!d || !k || !z || !out_sig || !out_recid || !ok))) return h.rc;
+    return staged(ctx, n, {{d, &ctx->in0, h.L, SECRET}, {k, &ctx->in3, h.L, SECRET}, {z, &ctx->in2, h.L}},
+                  {{out_sig, &ctx->out0, 2 * h.L}, {out_recid, &ctx->out2, 1}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_sign_batch_dev(ctx, curve, in[0], in[1], in[2], m, normalize_s, out[0], out[1], out[2]);
+                  });
+}
+
+int ecgpu_ecdsa_sign_rfc6979_batch(ecgpu_ctx* ctx, int curve, const uint8_t* d, const uint8_t* z, size_t n, int normalize_s,
+                                   uint8_t* out_sig, uint8_t* out_recid, uint8_t* ok) {
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!d || !z || !out_sig || !out_recid || !ok))) return h.rc;
+    return staged(ctx, n, {{d, &ctx->in0, h.L, SECRET}, {z, &ctx->in2, h.L}},
+                  {{out_sig, &ctx->out0, 2 * h.L}, {out_recid, &ctx->out2, 1}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_sign_rfc6979_batch_dev(ctx, curve, in[0], in[1], m, normalize_s, out[0], out[1], out[2]);
+                  });
+}
+
+int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx* ctx, int curve, const uint8_t* d, const uint8_t* msgs, size_t msg_len, size_t n, int normalize_s,
+                               uint8_t* out_sig, uint8_t* out_recid, uint8_t* ok) {
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!d || !out_sig || !out_recid || !ok || (msg_len && !msgs)))) return h.rc;
+    return staged(ctx, n, {{d, &ctx->in0, h.L, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}},
+                  {{out_sig, &ctx->out0, 2 * h.L}, {out_recid, &ctx->out2, 1}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_ecdsa_sign_msg_batch_dev(ctx, curve, in[0], in[1], msg_len, m, normalize_s, out[0], out[1], out[2]);
+                  });
+}
+
+int ecgpu_schnorr_sign_raw_batch(ecgpu_ctx* ctx, const uint8_t* sk, const uint8_t* msgs, size_t msg_len, const uint8_t* aux_rand, size_t n,
+                                 uint8_t* out_sig, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_K256);
+    if (h.bad(n && (!sk || !aux_rand || !out_sig || !ok || (msg_len && !msgs)))) return h.rc;
+    return staged(ctx, n, {{sk, &ctx->in0, 32, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {aux_rand, &ctx->in3, 32, SECRET}},
+                  {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return ecgpu_schnorr_sign_raw_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0], out[1]);
                   });
 }
 

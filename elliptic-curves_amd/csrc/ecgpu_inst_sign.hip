@@ -1,0 +1,59 @@
+// ecgpu_inst_sign.hip — instantiates the signing kernels (ecgpu_sign.h) for -DECGPU_CURVE=...; a translation unit of its own so
+// that tools/ct_isa_check.py --unit sign can look at exactly these kernels, and so that the HMAC bodies build beside the rest
+#include "ecgpu_sign.h"
+#include "ecgpu_launch.h"
+
+namespace ecgpu {
+
+using CurveT = ECGPU_CURVE;
+
+namespace {
+inline unsigned sign_grid(size_t n) { return (unsigned)((n + BLOCK - 1) / BLOCK); }
+
+// BIP340 exists over secp256k1 only: the other curves' translation units hold no Schnorr kernel
+template <class C>
+void schnorr_nonce_impl(hipStream_t s, const uint8_t* sk, const uint8_t* p_xy, const uint8_t* aux, const uint8_t* msgs, size_t msg_len,
+                        size_t n, uint8_t* dp_out, uint8_t* k_out, uint8_t* flag) {
+    if constexpr (C::ID == CURVE_K256)
+        hipLaunchKernelGGL(k_schnorr_nonce<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, sk, p_xy, aux, msgs, msg_len, n, dp_out, k_out, flag);
+}
+template <class C>
+void schnorr_finish_impl(hipStream_t s, const uint8_t* dp, const uint8_t* k, const uint8_t* flag, const uint8_t* r_xy,
+                         const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* sig, uint8_t* ok) {
+    if constexpr (C::ID == CURVE_K256)
+        hipLaunchKernelGGL(k_schnorr_sign_finish<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, dp, k, flag, r_xy, r_inf, msgs, msg_len, n,
+                           sig, ok);
+}
+}  // namespace
+
+template <> void launch_sign_nonce_load<CurveT>(hipStream_t s, const uint8_t* k_in, size_t n, uint8_t* k_out, uint8_t* flag) {
+    hipLaunchKernelGGL(k_sign_nonce_load<CurveT>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, k_in, n, k_out, flag);
+}
+template <> void launch_sign_hash_msg<CurveT>(hipStream_t s, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* z_out) {
+    hipLaunchKernelGGL(k_sign_hash_msg<CurveT>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, msgs, msg_len, n, z_out);
+}
+template <> size_t rfc6979_state_bytes<CurveT>() { return rfc6979_state_bytes_of<CurveT>(); }
+template <> void launch_rfc6979<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* z, size_t n, int cap, uint8_t* k_out,
+                                        uint8_t* flag, void* state) {
+    hipLaunchKernelGGL(k_rfc6979_first<CurveT>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, z, n, k_out, flag, state);
+    hipLaunchKernelGGL(k_rfc6979_retry<CurveT>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, z, n, cap, k_out, flag,
+                       (const void*)state);
+}
+template <> void launch_ecdsa_sign_finish<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag,
+                                                  const uint8_t* z, const uint8_t* r_xy, const uint8_t* r_inf, size_t n,
+                                                  int normalize_s, uint8_t* sig, uint8_t* recid, uint8_t* ok) {
+    hipLaunchKernelGGL(k_ecdsa_sign_finish<CurveT>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, k, k_flag, z, r_xy, r_inf, n, normalize_s,
+                       sig, recid, ok);
+}
+template <> void launch_schnorr_nonce<CurveT>(hipStream_t s, const uint8_t* sk, const uint8_t* p_xy, const uint8_t* aux,
+                                              const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* dp_out, uint8_t* k_out,
+                                              uint8_t* flag) {
+    schnorr_nonce_impl<CurveT>(s, sk, p_xy, aux, msgs, msg_len, n, dp_out, k_out, flag);
+}
+template <> void launch_schnorr_sign_finish<CurveT>(hipStream_t s, const uint8_t* dp, const uint8_t* k, const uint8_t* flag,
+                                                    const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len,
+                                                    size_t n, uint8_t* sig, uint8_t* ok) {
+    schnorr_finish_impl<CurveT>(s, dp, k, flag, r_xy, r_inf, msgs, msg_len, n, sig, ok);
+}
+
+}  // namespace ecgpu

@@ -111,6 +111,24 @@ template <class C> void launch_fixed_base_ct(hipStream_t s, const uint8_t* scala
 template <class C> void launch_xyz_mul_ct(hipStream_t s, const uint8_t* scalars, const uint8_t* xyz, size_t n, uint32_t* tab,
                                           size_t slots, uint32_t* proj_out, uint8_t* flags, int* status);   // projective records
 
+// ---- group "sign": signing around launch_fixed_base_ct (ecgpu_sign.h) ----
+// k as read -> k, or 1 outside [1, n); flag = the verdict
+template <class C> void launch_sign_nonce_load(hipStream_t s, const uint8_t* k_in, size_t n, uint8_t* k_out, uint8_t* flag);
+template <class C> void launch_sign_hash_msg(hipStream_t s, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* z_out);
+template <class C> size_t rfc6979_state_bytes();       // generator state per element between the two kernels of launch_rfc6979
+// k_rfc6979_first, then k_rfc6979_retry once (the deliberately variable-time one); cap: candidates per element
+template <class C> void launch_rfc6979(hipStream_t s, const uint8_t* d, const uint8_t* z, size_t n, int cap, uint8_t* k_out, uint8_t* flag,
+                                       void* state);
+template <class C> void launch_ecdsa_sign_finish(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* z,
+                                                 const uint8_t* r_xy, const uint8_t* r_inf, size_t n, int normalize_s, uint8_t* sig,
+                                                 uint8_t* recid, uint8_t* ok);
+// BIP340 (launches nothing for a curve other than k256); dp: d' || x(P), 64 bytes per element
+template <class C> void launch_schnorr_nonce(hipStream_t s, const uint8_t* sk, const uint8_t* p_xy, const uint8_t* aux, const uint8_t* msgs,
+                                             size_t msg_len, size_t n, uint8_t* dp_out, uint8_t* k_out, uint8_t* flag);
+template <class C> void launch_schnorr_sign_finish(hipStream_t s, const uint8_t* dp, const uint8_t* k, const uint8_t* flag,
+                                                   const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len, size_t n,
+                                                   uint8_t* sig, uint8_t* ok);
+
 // ---- group "msm": Pippenger pipeline ----
 template <class C> MsmPlan msm_plan(size_t n, int force_c, bool glv);
 template <class C> bool msm_use_glv(size_t n);          // k256: GLV halves for this term count?

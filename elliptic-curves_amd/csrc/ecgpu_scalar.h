@@ -11,6 +11,18 @@
 
 namespace ecgpu {
 
+// all ones / all zeros from a flag, opaque to the optimiser on the device (the ct_mask of ecgpu_ctmul.h, for this header's own
+// selections): a select under it stays a select.  Signing runs this arithmetic on secret scalars, and left to itself the compiler
+// turned `borrow ? a : d` inside the reduction loop of reduce_wire into an exec-masked block of moves (tools/ct_isa_check.py
+// --unit sign found it).
+ECGPU_HD uint32_t sn_mask(bool flag) {
+    uint32_t m = 0u - (uint32_t)flag;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(m));
+#endif
+    return m;
+}
+
 template <class C>
 struct ScalarN {
     ECGPU_CONST int N = C::N;
@@ -20,9 +32,9 @@ struct ScalarN {
     // a mod n for a < 2^(32 N) < 2n
     static ECGPU_HD void reduce_once(uint32_t* r, const uint32_t* a) {
         uint32_t d[N];
-        uint32_t borrow = mp_sub<N>(d, a, C::ORDER);
+        const uint32_t m = sn_mask(mp_sub<N>(d, a, C::ORDER) != 0);
 #pragma unroll
-        for (int i = 0; i < N; i++) r[i] = borrow ? a[i] : d[i];
+        for (int i = 0; i < N; i++) r[i] = (a[i] & m) | (d[i] & ~m);
     }
     // a wire-sized value (a message digest, an x coordinate) mod n.  One conditional subtraction where the wire size is
     // the size of n; a 66-byte p521 value can be 2^7 times n (n = 2^521 - 2^260..): up to 128 subtractions there.
@@ -88,7 +100,7 @@ struct ScalarN {
     static ECGPU_HD bool is_high(const uint32_t* a) {
         uint32_t twice[N];
         uint32_t carry = mp_add<N>(twice, a, a);
-        return carry || mp_geq<N>(twice, C::ORDER);          // 2a >= n  <=>  a > (n-1)/2 for odd n
+        return (bool)((int)(carry != 0) | (int)mp_geq<N>(twice, C::ORDER));   // 2a >= n  <=>  a > (n-1)/2 for odd n; | on purpose: no short circuit
     }
 };
 

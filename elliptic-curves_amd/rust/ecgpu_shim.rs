@@ -495,6 +495,95 @@ pub mod gpu {
         })?;
         Some(xy.chunks(2 * l).zip(ok).map(|(c, f)| if f != 0 { Some(elliptic_curve::group::Curve::to_affine(&point_from_wire::<C>(c, 0))) } else { None }).collect())
     }
+
+    /// One ECDSA signature of a batch: `(r || s, RecoveryId byte)`, or `None` where the reference returns `Err` (r = 0 or s = 0,
+    /// no nonce within the generator's candidate limit).
+    pub type BatchSig = Option<(Vec<u8>, u8)>;
+
+    fn sigs_from_wire(l: usize, sig: Vec<u8>, recid: Vec<u8>, ok: Vec<u8>) -> Vec<BatchSig> {
+        sig.chunks(2 * l).zip(recid).zip(ok).map(|((s, id), f)| if f != 0 { Some((s.to_vec(), id)) } else { None }).collect()
+    }
+
+    /// Batch form of `PrehashSigner::sign_prehash` of `ecdsa::SigningKey<C>` (ecdsa 0.17.0; instantiated at k256/src/ecdsa.rs,
+    /// p256/src/ecdsa.rs, p384/src/ecdsa.rs): `d` the signing keys, `z` = `bits2field(prehash)`.  The RFC 6979 nonce, R = k G on
+    /// the uniform-schedule kernel, k^-1 and s are computed on the device (`ecgpu_ecdsa_sign_rfc6979_batch`); the wire copy of the
+    /// keys is wiped here, the device side by the library.  `normalize_s` = `C::NORMALIZE_S`.
+    pub fn batch_sign_prehash<C: GpuCurve>(d: &[Sc<C>], z: &[FieldBytes<C>], normalize_s: bool) -> Option<Vec<BatchSig>>
+    where
+        C::FieldBytesSize: ModulusSize,
+    {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = d.len();
+        assert!(z.len() == n);
+        let l = field_len::<C>();
+        let keys = secret_scalars_to_wire::<C>(d.iter().copied());
+        let zz: Vec<u8> = z.iter().flat_map(|b| b.as_ref().to_vec()).collect();
+        let (mut sig, mut recid, mut ok) = (vec![0u8; n * 2 * l], vec![0u8; n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_ecdsa_sign_rfc6979_batch(eng.0, C::ID, keys.as_ptr(), zz.as_ptr(), n, normalize_s as c_int, sig.as_mut_ptr(),
+                                           recid.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sigs_from_wire(l, sig, recid, ok))
+    }
+
+    /// Batch form of `Signer::sign(msg)` for messages of one length: the curve's `DigestAlgorithm` runs on the device too
+    /// (`ecgpu_ecdsa_sign_msg_batch`).
+    pub fn batch_sign<C: GpuCurve>(d: &[Sc<C>], msgs: &[u8], msg_len: usize, normalize_s: bool) -> Option<Vec<BatchSig>>
+    where
+        C::FieldBytesSize: ModulusSize,
+    {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = d.len();
+        assert!(msgs.len() == n * msg_len);
+        let l = field_len::<C>();
+        let keys = secret_scalars_to_wire::<C>(d.iter().copied());
+        let (mut sig, mut recid, mut ok) = (vec![0u8; n * 2 * l], vec![0u8; n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_ecdsa_sign_msg_batch(eng.0, C::ID, keys.as_ptr(), msgs.as_ptr(), msg_len, n, normalize_s as c_int, sig.as_mut_ptr(),
+                                       recid.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sigs_from_wire(l, sig, recid, ok))
+    }
+
+    /// The hazmat form with the caller's nonces (`ecdsa::hazmat::sign_prehashed`; `ecdsa_core::new_signing_test!`,
+    /// p256/src/ecdsa.rs:156-159): known-answer tests, and callers with a nonce source of their own.
+    pub fn batch_sign_prehashed_with_nonce<C: GpuCurve>(d: &[Sc<C>], k: &[Sc<C>], z: &[FieldBytes<C>], normalize_s: bool)
+                                                        -> Option<Vec<BatchSig>>
+    where
+        C::FieldBytesSize: ModulusSize,
+    {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = d.len();
+        assert!(k.len() == n && z.len() == n);
+        let l = field_len::<C>();
+        let (keys, nonces) = (secret_scalars_to_wire::<C>(d.iter().copied()), secret_scalars_to_wire::<C>(k.iter().copied()));
+        let zz: Vec<u8> = z.iter().flat_map(|b| b.as_ref().to_vec()).collect();
+        let (mut sig, mut recid, mut ok) = (vec![0u8; n * 2 * l], vec![0u8; n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_ecdsa_sign_batch(eng.0, C::ID, keys.as_ptr(), nonces.as_ptr(), zz.as_ptr(), n, normalize_s as c_int, sig.as_mut_ptr(),
+                                   recid.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sigs_from_wire(l, sig, recid, ok))
+    }
+
+    /// Batch form of `k256::schnorr::SigningKey::sign_raw(msg, aux_rand)` (k256/src/schnorr/signing.rs:97-137) from the secret
+    /// key BYTES, with the even-y fix-up of `From<NonZeroScalar>` (:146-167) on the device: messages of one length.
+    /// `None` per element where `SigningKey::from_bytes` or `sign_raw` returns `Err`.
+    pub fn schnorr_batch_sign_raw(sk: &[Zeroizing<[u8; 32]>], msgs: &[u8], msg_len: usize, aux_rand: &[[u8; 32]]) -> Option<Vec<Option<[u8; 64]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = sk.len();
+        assert!(aux_rand.len() == n && msgs.len() == n * msg_len);
+        let mut keys = Zeroizing::new(Vec::with_capacity(32 * n));
+        for k in sk {
+            keys.extend_from_slice(&k[..]);
+        }
+        let (mut sig, mut ok) = (vec![0u8; 64 * n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_schnorr_sign_raw_batch(eng.0, keys.as_ptr(), msgs.as_ptr(), msg_len, aux_rand.as_ptr() as *const u8, n,
+                                         sig.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sig.chunks(64).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
+    }
 }
 
 // =====================================================================================================================
@@ -565,6 +654,24 @@ pub mod gpu {
 //
 //     and `k256/src/schnorr/verifying.rs:76-99` / `k256/src/ecdsa.rs` gain `verify_batch` functions built on
 //     `ecgpu::gpu::batch_verify_prehashed` resp. `ecgpu_schnorr_verify_raw_batch`.
+//
+// (3b) signing.  `k256/src/schnorr/signing.rs:97-137` gains, next to `sign_raw`,
+//
+//         #[cfg(feature = "gpu")]
+//         pub fn sign_raw_batch(keys: &[Zeroizing<[u8; 32]>], msgs: &[u8], msg_len: usize, aux: &[[u8; 32]]) -> Vec<Result<Signature>>
+//
+//     on `ecgpu::gpu::schnorr_batch_sign_raw` (fallback: `SigningKey::from_bytes(k)?.sign_raw(msg, aux)` per element), and the
+//     ECDSA curves (k256 / p256 / p384 `ecdsa.rs`) a batch type over `ecdsa::SigningKey<C>`,
+//
+//         #[cfg(feature = "gpu")]
+//         pub struct BatchSigner<'a>(pub &'a [SigningKey]);
+//         impl BatchSigner<'_> {
+//             pub fn sign_prehash(&self, prehashes: &[&[u8]]) -> Vec<Result<(Signature, RecoveryId)>> { .. }
+//         }
+//
+//     whose `sign_prehash` maps every prehash through `bits2field` and calls `ecgpu::gpu::batch_sign_prehash::<C>` with
+//     `C::NORMALIZE_S` (fallback: `PrehashSigner::sign_prehash` per key); `BatchSigner::sign(msgs, msg_len)` goes to
+//     `ecgpu::gpu::batch_sign`.  The signatures are byte-identical to the reference's (tests/golden/signing.json).
 //
 // (4) primeorder curves select their generator-multiplication backend through `PrimeCurveParams::Backend`
 //     (primeorder/src/lib.rs:62; p256/src/arithmetic/tables.rs:24-44).  `GpuBackend` below is such a backend: single calls

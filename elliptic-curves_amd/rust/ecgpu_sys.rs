@@ -579,6 +579,96 @@ unsafe extern "C" {
         d_out_xy: *mut c_void,
         d_out_inf: *mut c_void,
     ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_batch(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d: *const u8,
+        k: *const u8,
+        z: *const u8,
+        n: usize,
+        normalize_s: c_int,
+        out_sig: *mut u8,
+        out_recid: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_batch_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_d: *const c_void,
+        d_k: *const c_void,
+        d_z: *const c_void,
+        n: usize,
+        normalize_s: c_int,
+        d_out_sig: *mut c_void,
+        d_out_recid: *mut c_void,
+        d_ok: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_rfc6979_batch(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d: *const u8,
+        z: *const u8,
+        n: usize,
+        normalize_s: c_int,
+        out_sig: *mut u8,
+        out_recid: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_rfc6979_batch_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_d: *const c_void,
+        d_z: *const c_void,
+        n: usize,
+        normalize_s: c_int,
+        d_out_sig: *mut c_void,
+        d_out_recid: *mut c_void,
+        d_ok: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_msg_batch(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        n: usize,
+        normalize_s: c_int,
+        out_sig: *mut u8,
+        out_recid: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_ecdsa_sign_msg_batch_dev(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        d_d: *const c_void,
+        d_msgs: *const c_void,
+        msg_len: usize,
+        n: usize,
+        normalize_s: c_int,
+        d_out_sig: *mut c_void,
+        d_out_recid: *mut c_void,
+        d_ok: *mut c_void,
+    ) -> c_int;
+    pub fn ecgpu_schnorr_sign_raw_batch(
+        ctx: *mut EcgpuCtx,
+        sk: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        aux_rand: *const u8,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_schnorr_sign_raw_batch_dev(
+        ctx: *mut EcgpuCtx,
+        d_sk: *const c_void,
+        d_msgs: *const c_void,
+        msg_len: usize,
+        d_aux_rand: *const c_void,
+        n: usize,
+        d_out_sig: *mut c_void,
+        d_ok: *mut c_void,
+    ) -> c_int;
     pub fn ecgpu_batch_mul_ct_xyz(
         ctx: *mut EcgpuCtx,
         curve: c_int,

@@ -547,6 +547,57 @@ int ecgpu_lincomb_ct(ecgpu_ctx *ctx, int curve, const uint8_t *scalars, const ui
 int ecgpu_lincomb_ct_dev(ecgpu_ctx *ctx, int curve, const void *d_scalars, const void *d_points_xy, const void *d_points_inf,
                          size_t n, void *d_out_xy, void *d_out_inf);
 
+/* ---- batch signing: ECDSA (the caller's nonce or RFC 6979) and BIP340 Schnorr ---------------------------------------------
+ * The secret-scalar consumers of ecgpu_batch_mul_base_ct inside the library: every R = k G (and the Schnorr P = d G) is that
+ * entry's kernel, and the kernels around it keep its rule — no branch and no address depends on a key, a nonce, a digest or
+ * anything derived from them (tools/ct_isa_check.py --unit sign; tests/test_sign_isa.py).  k^-1 is one branch-free
+ * division-step inversion per element.  Two pieces are variable-time, both on purpose: the RFC 6979 retry loop
+ * (k_rfc6979_retry), whose trip count depends on the candidates it REJECTED — never used, and what the `loop` of the
+ * reference's `generate_k` reveals — and, as for every entry point, `to_affine` of the public R.  Everything the call derives
+ * from d, k or aux_rand on the device (the HMAC K / V state, nonces, projective and affine R, the staged copies of a
+ * host-pointer call) is zeroed behind its last kernel, in stream order; ecgpu_wipe covers the same buffers.
+ * An element that cannot be signed never fails the batch: it gets a zero record, recid 0 and ok[i] = 0, and its neighbours are
+ * untouched.  Invalid keys and nonces are replaced under a mask, not branched on.
+ *
+ * ecgpu_ecdsa_sign_batch — the hazmat form with the caller's nonce: `ecdsa::hazmat::sign_prehashed` as `ecdsa_core::
+ *   new_signing_test!` runs it (p256/src/ecdsa.rs:156-159).  d, k, z: n*L bytes each, big-endian; z = bits2field(prehash) is
+ *   reduced mod n on the device as in ecgpu_ecdsa_verify_batch.  R = k G, r = x(R) mod n, s = k^-1 (z + r d) mod n.
+ *   normalize_s != 0 is the curve's `NORMALIZE_S` (true for k256, k256/src/ecdsa.rs:104-106; false for p256): s > (n-1)/2
+ *   becomes n - s and bit 0 of the recovery id flips.  out_sig: n*2L bytes r || s.  out_recid[i]: the byte
+ *   ecgpu_ecdsa_recover_batch takes — bit 0 = y(R) odd, bit 1 = x(R) >= n.  ok[i] = 1 iff 1 <= d < n, 1 <= k < n, r != 0 and
+ *   s != 0.  The ten ECDSA parameter sets; ECGPU_SM2 and ECGPU_BIGN256 return ECGPU_ERR_CURVE.
+ * ecgpu_ecdsa_sign_rfc6979_batch — `PrehashSigner::sign_prehash` of `ecdsa::SigningKey<C>`: the nonce of RFC 6979 section 3.2
+ *   generated on the device, HMAC over the curve's `DigestAlgorithm` (SHA-256: k256, p256, bp256; SHA-384: p384, bp384;
+ *   SHA-224: p224; SHA-512: p521), x = d as L bytes, h1 = (z mod n) as L bytes, no additional data; a candidate is the first L
+ *   bytes of T shifted right by 8L - bitlen(n) (7 bits for p521), accepted iff 1 <= k < n; after 128 rejected candidates
+ *   ok[i] = 0.  ECGPU_ERR_CURVE also for ECGPU_P192 (no `DigestAlgorithm`, p192/src/ecdsa.rs).
+ * ecgpu_ecdsa_sign_msg_batch — `Signer::sign(msg)`: the curve's digest of message i on the device (as in
+ *   ecgpu_ecdsa_verify_msg_batch), z = bits2field(digest), then the RFC 6979 form.  msgs: n*msg_len bytes, one uniform length
+ *   per call, 0 allowed.
+ * ecgpu_schnorr_sign_raw_batch — `SigningKey::sign_raw(msg, aux_rand)` (k256/src/schnorr/signing.rs:97-137) with the key
+ *   fix-up of `From<NonZeroScalar>` (:146-167); secp256k1 only.  sk n*32, msgs n*msg_len, aux_rand n*32 bytes, out_sig n*64
+ *   bytes x(R) || s.  P = d G, d <- n - d if y(P) is odd, t = tagged_hash("BIP0340/aux", aux) ^ d, k = tagged_hash(
+ *   "BIP0340/nonce", t || x(P) || msg) mod n, R = k G, k <- n - k if y(R) is odd, e = tagged_hash("BIP0340/challenge",
+ *   x(R) || x(P) || msg) mod n, s = k + e d.  ok[i] = 0 for d = 0, d >= n, k = 0 or s = 0.
+ * Device pointers: 16-byte aligned bases as everywhere.  Asynchronous contexts and deferred errors behave as for the other `_ct`
+ * calls. */
+int ecgpu_ecdsa_sign_batch(ecgpu_ctx *ctx, int curve, const uint8_t *d, const uint8_t *k, const uint8_t *z, size_t n,
+                           int normalize_s, uint8_t *out_sig, uint8_t *out_recid, uint8_t *ok);
+int ecgpu_ecdsa_sign_batch_dev(ecgpu_ctx *ctx, int curve, const void *d_d, const void *d_k, const void *d_z, size_t n,
+                               int normalize_s, void *d_out_sig, void *d_out_recid, void *d_ok);
+int ecgpu_ecdsa_sign_rfc6979_batch(ecgpu_ctx *ctx, int curve, const uint8_t *d, const uint8_t *z, size_t n, int normalize_s,
+                                   uint8_t *out_sig, uint8_t *out_recid, uint8_t *ok);
+int ecgpu_ecdsa_sign_rfc6979_batch_dev(ecgpu_ctx *ctx, int curve, const void *d_d, const void *d_z, size_t n, int normalize_s,
+                                       void *d_out_sig, void *d_out_recid, void *d_ok);
+int ecgpu_ecdsa_sign_msg_batch(ecgpu_ctx *ctx, int curve, const uint8_t *d, const uint8_t *msgs, size_t msg_len, size_t n,
+                               int normalize_s, uint8_t *out_sig, uint8_t *out_recid, uint8_t *ok);
+int ecgpu_ecdsa_sign_msg_batch_dev(ecgpu_ctx *ctx, int curve, const void *d_d, const void *d_msgs, size_t msg_len, size_t n,
+                                   int normalize_s, void *d_out_sig, void *d_out_recid, void *d_ok);
+int ecgpu_schnorr_sign_raw_batch(ecgpu_ctx *ctx, const uint8_t *sk, const uint8_t *msgs, size_t msg_len,
+                                 const uint8_t *aux_rand, size_t n, uint8_t *out_sig, uint8_t *ok);
+int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx *ctx, const void *d_sk, const void *d_msgs, size_t msg_len,
+                                     const void *d_aux_rand, size_t n, void *d_out_sig, void *d_ok);
+
 /* The same two with projective points: point i is the record X || Y || Z of the wire format above (3L bytes, no flag array),
  * as the reference's `Mul<Scalar>` and `lincomb` take a `ProjectivePoint`.  For every input the results and the return code
  * are those of `to_affine` applied to each record followed by ecgpu_batch_mul_ct / ecgpu_lincomb_ct: X, Y or Z >= p, and a

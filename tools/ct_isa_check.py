@@ -4,6 +4,10 @@ address may depend on the contents of a scalar or point record.
 
     python tools/ct_isa_check.py [--curve P256Params ...] [--kernels k_var_base_ct,k_fixed_base_ct,k_proj_sum_level] [--keep] [--self-test]
 (k_proj_sum_level: the tree of complete additions ecgpu_lincomb_ct runs over the products of k_var_base_ct)
+    python tools/ct_isa_check.py --unit sign [--curve ...] [--kernels ...] [--must-flag k_rfc6979_retry]
+the signing kernels (csrc/ecgpu_sign.h, translation unit ecgpu_inst_sign.hip) under the same rule: keys, nonces, digests, the
+HMAC state and the affine R are all loaded records.  --must-flag names kernels that MUST be reported — k_rfc6979_retry, the
+retry loop whose trip count depends on the rejected candidates on purpose: reporting it shows that the analysis sees these kernels.
 
 How: the translation unit is compiled to assembly (hipcc -S --offload-device-only; no GPU needed) and every selected kernel
 goes through a forward taint analysis over its control-flow graph (register-precise, iterated to a fixed point):
@@ -362,12 +366,21 @@ def summarize(body):
     return ", ".join("%s x%d" % kv for kv in sorted(c.items()))
 
 
-def check(asm, wanted, verbose=False):
+# translation unit and default kernel selection of --unit
+UNITS = {
+    "ct": ("ecgpu_inst_ct.hip", "k_var_base_ct,k_fixed_base_ct,k_proj_sum_level"),
+    "sign": ("ecgpu_inst_sign.hip", "k_rfc6979_first,k_schnorr_nonce,k_ecdsa_sign_finish,k_schnorr_sign_finish,k_sign_nonce_load"),
+}
+
+
+def check(asm, wanted, verbose=False, seen_names=None):
     total = 0
     kernels = parse_kernels(asm)
     for name, body in kernels.items():
         if not any(w in name for w in wanted):
             continue
+        if seen_names is not None:
+            seen_names.update(w for w in wanted if w in name)
         n_ins = sum(1 for _, i in body if i is not None)
         if n_ins == 0:
             continue
@@ -389,13 +402,17 @@ def check(asm, wanted, verbose=False):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="append")
-    ap.add_argument("--kernels", default="k_var_base_ct,k_fixed_base_ct,k_proj_sum_level")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, or the signing kernels")
+    ap.add_argument("--kernels", help="default: the data-independent kernels of the unit")
+    ap.add_argument("--must-flag", default="", help="kernels of the unit that must be reported (comma-separated)")
     ap.add_argument("--asm", help="check an existing .s file instead of compiling")
     ap.add_argument("--keep", action="store_true")
     ap.add_argument("--self-test", action="store_true", help="the variable-time kernels must be flagged")
     a = ap.parse_args()
     curves = a.curve or ["K256Params", "P256Params", "P384Params"]
-    wanted = a.kernels.split(",")
+    tu, default_kernels = UNITS[a.unit]
+    wanted = (a.kernels or default_kernels).split(",")
+    must_flag = [k for k in a.must_flag.split(",") if k]
     if a.asm:
         return check(a.asm, wanted)
     bad = 0
@@ -412,10 +429,20 @@ def main():
                 print("SELF-TEST FAILED: a variable-time kernel went unreported")
                 bad += 1
         else:
-            asm = os.path.join(tmp, "ct_%s.s" % c)
-            compile_asm("ecgpu_inst_ct.hip", c, asm)
+            asm = os.path.join(tmp, "%s_%s.s" % (a.unit, c))
+            compile_asm(tu, c, asm)
             print("== %s" % c)
-            bad += check(asm, wanted)
+            found = set()
+            bad += check(asm, wanted, seen_names=found)
+            for w in wanted:
+                if w not in found and not (w.startswith("k_schnorr") and c != "K256Params"):      # BIP340 exists over secp256k1 only
+                    print("NOT FOUND: no kernel matches %s" % w)
+                    bad += 1
+            for k in must_flag:
+                print("-- %s (violations expected)" % k)
+                if check(asm, [k]) == 0:
+                    print("MUST-FLAG FAILED: %s went unreported" % k)
+                    bad += 1
     if not a.keep:
         for f in os.listdir(tmp):
             os.unlink(os.path.join(tmp, f))
