@@ -146,22 +146,8 @@ namespace {
         }                                                                                       \
     } while (0)
 
-int ensure(ecgpu_ctx* ctx, DevBuf& b, size_t bytes) {
-    if (bytes > b.dirty) b.dirty = bytes;
-    if (bytes <= b.cap) return ECGPU_OK;
-    if (b.p) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        HIP_TRY(ctx, hipFree(b.p));
-        b.p = nullptr;
-        b.cap = 0;
-    }
-    size_t want = bytes + bytes / 8 + 4096;
-    HIP_TRY(ctx, hipMalloc(&b.p, want));
-    b.cap = want;
-    return ECGPU_OK;
-}
-
-// the same for a buffer that is used on another stream of the context (an MSM lane)
+// grows a scratch buffer to `bytes`; a buffer that has to move is freed behind the work of `stream`, the stream of the context
+// it is used on (the context's own, or an MSM lane's)
 int ensure_on(ecgpu_ctx* ctx, hipStream_t stream, DevBuf& b, size_t bytes) {
     if (bytes > b.dirty) b.dirty = bytes;
     if (bytes <= b.cap) return ECGPU_OK;
@@ -176,6 +162,7 @@ int ensure_on(ecgpu_ctx* ctx, hipStream_t stream, DevBuf& b, size_t bytes) {
     b.cap = want;
     return ECGPU_OK;
 }
+inline int ensure(ecgpu_ctx* ctx, DevBuf& b, size_t bytes) { return ensure_on(ctx, ctx->stream, b, bytes); }
 
 template <class F>
 int dispatch(int curve, F&& f) {
@@ -315,16 +302,36 @@ void resolve_timing(ecgpu_ctx* ctx) {
     ctx->spans.clear();
 }
 
+// The spans of a call: stage name -> the pair of event marks around it (record).  The three-span default, and the variants of the
+// MSM (with and without the detail marks of MsmPlan), of ecgpu_lincomb_ct, of the verifiers ("recode" = their prepare kernel) and
+// of the calls without a normalisation of their own (ecgpu_msm_parts_dev, ecgpu_batch_decompress_dev).
+// "accumulate" is the accumulation kernel alone; "reduce" = everything after it = "finish" (bucket finish + running sums) +
+// "tree" (over the segment sums) + "combine" (window sums, Horner chain, conversion to affine); "sort" = "prepare" + the sort
+struct Span { const char* name; int from, to; };
+struct SpanList {
+    const Span* p;
+    size_t n;
+    template <size_t N> constexpr SpanList(const Span (&a)[N]) : p(a), n(N) {}
+};
+constexpr Span SPANS_DEFAULT[] = {{"main", 0, 1}, {"normalize", 1, 2}, {"total", 0, 2}};
+constexpr Span SPANS_MSM[] = {{"main", 0, 1}, {"normalize", 1, 2}, {"total", 0, 2}, {"sort", 0, 3}, {"accumulate", 3, 4}, {"reduce", 4, 1}};
+constexpr Span SPANS_MSM_DETAIL[] = {{"main", 0, 1}, {"normalize", 1, 2}, {"total", 0, 2}, {"sort", 0, 3}, {"accumulate", 3, 4},
+                                     {"reduce", 4, 1}, {"prepare", 0, 6}, {"finish", 4, 7}, {"tree", 7, 8}, {"combine", 8, 1}};
+constexpr Span SPANS_LINCOMB_CT[] = {{"main", 0, 1}, {"normalize", 1, 2}, {"total", 0, 2}, {"accumulate", 0, 3}, {"reduce", 3, 1}};
+constexpr Span SPANS_VERIFY[] = {{"recode", 0, 3}, {"main", 3, 1}, {"normalize", 1, 2}, {"total", 0, 2}};
+constexpr Span SPANS_MSM_PARTS[] = {{"main", 0, 1}, {"total", 0, 1}, {"sort", 0, 3}, {"accumulate", 3, 4}, {"reduce", 4, 1}};
+constexpr Span SPANS_NO_NORMALIZE[] = {{"main", 0, 1}, {"total", 0, 1}};
+
 // the spans of the call just made; turned into milliseconds now, or (asynchronous mode: the events have not happened
 // yet) when ecgpu_last_timing asks
-void collect_timing(ecgpu_ctx* ctx, std::initializer_list<std::pair<const char*, std::pair<int, int>>> spans) {
+void collect_timing(ecgpu_ctx* ctx, SpanList spans) {
     ctx->spans.clear();
     ctx->lane_last = -1;
     if (!ctx->timing_on) {                     // no events were recorded for this call: ecgpu_last_timing has nothing to report
         ctx->timing.clear();
         return;
     }
-    for (auto& s : spans) ctx->spans.emplace_back(s.first, s.second);
+    for (size_t i = 0; i < spans.n; i++) ctx->spans.emplace_back(spans.p[i].name, std::make_pair(spans.p[i].from, spans.p[i].to));
     if (!ctx->async) resolve_timing(ctx);
 }
 
@@ -599,54 +606,76 @@ inline bool fixed_soa() {
 
 // ---- device-pointer implementations --------------------------------------------------------------------
 
+// The one call frame of the device-pointer pipelines (the counterpart of HostCall / staged below).  An implementation states
+//   what it does for an empty call, before the frame: a call that uses the comb table or the generator LUTs builds them for
+//       n == 0 too (ensure_table / ensure_ct_lut come first), a reducing call writes the identity, every other returns at once;
+//   what it reserves: {buffer, bytes[, wanted]} in order — grown before anything is queued;
+//   its wipe set: WIPE_* flags (0 for the variable-time forms), zeroed behind the call's last kernel on EVERY path out, early error
+//       returns included (CtWipe);
+//   its launches between marks: the constructor has joined the MSM lanes and cleared the status word (reset_status) before the
+//       first of them; mark(i) records event i; `normalized` is the usual tail (mark 1, normalize_out of ctx->proj, mark 2), `done`
+//       reads the status back (finish);
+//   its span table (collect_timing): SPANS_DEFAULT unless it says otherwise.
+struct Reserve { DevBuf& buf; size_t bytes; bool wanted = true; };
+struct DevCall {
+    ecgpu_ctx* ctx;
+    CtWipe wipe;
+    int rc = ECGPU_OK;         // not ECGPU_OK after the constructor: nothing was queued, the implementation returns it
+    DevCall(ecgpu_ctx* c, int wipe_set, std::initializer_list<Reserve> bufs) : ctx(c), wipe(c, wipe_set) {
+        for (const Reserve& r : bufs)
+            if (r.wanted && (rc = ensure(ctx, r.buf, r.bytes)) != ECGPU_OK) return;
+        rc = reset_status(ctx);
+    }
+    void mark(int i) { record(ctx, i); }
+    int done(SpanList spans = SPANS_DEFAULT) {
+        rc = finish(ctx);
+        collect_timing(ctx, spans);
+        return rc;
+    }
+    int done_unmarked() { return rc = finish(ctx); }      // a call that recorded no marks leaves the spans of the call before alone
+    template <class C>
+    int normalized(size_t n, void* d_out_xy, void* d_out_inf, SpanList spans = SPANS_DEFAULT, bool soa = false) {
+        mark(1);
+        if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf, soa)) != ECGPU_OK) return rc;
+        mark(2);
+        return done(spans);
+    }
+};
+
 template <class C>
 int mul_base_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out_xy, void* d_out_inf, bool compressed = false) {
-    constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
+    constexpr int NS = Field<C>::NS;
     int rc;
     if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    DevCall call(ctx, 0, {{ctx->proj, n * 3 * NS * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
     const Table& t = ctx->table[C::ID];
-    record(ctx, 0);
     const bool soa = !compressed && fixed_soa();
+    call.mark(0);
     launch_fixed_base<C>(ctx->stream, (const uint8_t*)d_scalars, n, (const uint32_t*)t.d, t.w, t.nwin, (uint32_t*)ctx->proj.p,
                          ctx->d_status, soa);
-    record(ctx, 1);
-    if (compressed) {
-        if ((rc = ensure(ctx, ctx->prefix, n * NS * 4)) != ECGPU_OK) return rc;
-        launch_normalize_compressed<C>(ctx->stream, (const uint32_t*)ctx->proj.p, (uint32_t*)ctx->prefix.p, n, (uint8_t*)d_out_xy,
-                                       (uint8_t*)d_out_inf);
-    } else if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf, soa)) != ECGPU_OK) {
-        return rc;
-    }
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    if (!compressed) return call.normalized<C>(n, d_out_xy, d_out_inf, SPANS_DEFAULT, soa);
+    call.mark(1);
+    if ((rc = ensure(ctx, ctx->prefix, n * NS * 4)) != ECGPU_OK) return rc;
+    launch_normalize_compressed<C>(ctx->stream, (const uint32_t*)ctx->proj.p, (uint32_t*)ctx->prefix.p, n, (uint8_t*)d_out_xy,
+                                   (uint8_t*)d_out_inf);
+    call.mark(2);
+    return call.done();
 }
 
 template <class C>
 int mul_var_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_points_xy, const void* d_points_inf, size_t n,
                 void* d_out_xy, void* d_out_inf) {
-    constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
+    constexpr int NS = Field<C>::NS;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    size_t tstride = var_base_slots<C>(n);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    const size_t tstride = var_base_slots<C>(n);
+    DevCall call(ctx, 0, {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_var_base<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
                        (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, ctx->d_status);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 
 // ---- uniform-schedule variants (ecgpu_ct.h): the reference's constant-time drivers as they are ---------------------------
@@ -656,19 +685,12 @@ int mul_base_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out
     int rc;
     if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
-    CtWipe wipe(ctx, WIPE_SCRATCH);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, WIPE_SCRATCH, {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
                             (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 
 // ---- signing (ecgpu_sign.h): nonce -> k G on the uniform-schedule fixed-base kernel -> affine R -> the finish kernel ------------
@@ -683,17 +705,12 @@ int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void*
     int rc;
     if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
-    CtWipe wipe(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->sg_k, n * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->sg_flag, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_xy, n * 2 * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
-    if (!d_k && (rc = ensure(ctx, ctx->sg_state, n * rfc6979_state_bytes<C>() + 16)) != ECGPU_OK) return rc;
-    if (from_msg && (rc = ensure(ctx, ctx->ec_e, n * L + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * L + 16}, {ctx->sg_flag, n + 16},
+                  {ctx->ec_xy, n * 2 * L + 16}, {ctx->ec_inf, n + 16}, {ctx->sg_state, n * rfc6979_state_bytes<C>() + 16, !d_k},
+                  {ctx->ec_e, n * L + 16, from_msg}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     if (from_msg) {
         launch_sign_hash_msg<C>(ctx->stream, (const uint8_t*)d_z, msg_len, n, (uint8_t*)ctx->ec_e.p);
         d_z = ctx->ec_e.p;
@@ -705,15 +722,13 @@ int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void*
                           (uint8_t*)ctx->sg_flag.p, ctx->sg_state.p);
     launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)ctx->sg_k.p, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
                             (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    record(ctx, 1);
+    call.mark(1);
     if ((rc = normalize_out<C>(ctx, n, ctx->ec_xy.p, ctx->ec_inf.p)) != ECGPU_OK) return rc;
     launch_ecdsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)ctx->sg_k.p, (const uint8_t*)ctx->sg_flag.p,
                                 (const uint8_t*)d_z, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, n, normalize_s,
                                 (uint8_t*)d_sig, (uint8_t*)d_recid, (uint8_t*)d_ok);
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    call.mark(2);
+    return call.done();
 }
 
 // xyz: d_points_xy holds projective records X || Y || Z (k_xyz_mul_ct) and d_points_inf is unused
@@ -722,61 +737,38 @@ int mul_var_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_points_x
                    void* d_out_xy, void* d_out_inf, bool xyz = false) {
     constexpr int NS = Field<C>::NS;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    CtWipe wipe(ctx, WIPE_SCRATCH);
-    size_t tstride = var_base_slots<C>(n);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    const size_t tstride = var_base_slots<C>(n);
+    DevCall call(ctx, WIPE_SCRATCH,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}, {ctx->ct_flags, n + 16}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     if (xyz)
         launch_xyz_mul_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, n, (uint32_t*)ctx->vtab.p, tstride,
                              (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     else
         launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
                               (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 
 template <class C>
 int normalize_dev(ecgpu_ctx* ctx, const void* d_xyz, size_t n, void* d_out_xy, void* d_out_inf) {
-    constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, 0, {{ctx->proj, n * 3 * Field<C>::NS * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_load_proj<C>(ctx->stream, (const uint8_t*)d_xyz, n, (uint32_t*)ctx->proj.p, ctx->d_status);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 
+// (a reducing call: the sum of no points is the identity, written by the same kernels)
 template <class C>
 int point_sum_dev(ecgpu_ctx* ctx, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy, void* d_out_inf) {
-    constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
-    int rc;
-    if ((rc = ensure(ctx, ctx->proj, 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, 0, {{ctx->proj, 3 * Field<C>::NS * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_point_sum<C>(ctx->stream, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, (uint32_t*)ctx->proj.p, ctx->d_status);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, 1, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(1, d_out_xy, d_out_inf);
 }
 
 // ---- projective points into the variable-time path: X || Y || Z records are normalised on the device (k_xyz_affine: one
@@ -793,19 +785,43 @@ int xyz_stage(ecgpu_ctx* ctx, hipStream_t s, const void* d_xyz, size_t n, DevBuf
     launch_xyz_affine<C>(s, (const uint8_t*)d_xyz, n, (uint32_t*)prefix.p, (uint8_t*)xy.p, (uint8_t*)inf.p, ctx->d_status);
     return ECGPU_OK;
 }
-// the same as the first stage of a call on the context's stream (the pattern of decode_compressed: the second stage runs under
-// KeepStatus)
-template <class C>
-int decode_xyz(ecgpu_ctx* ctx, const void* d_xyz, size_t n) {
-    int rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    return xyz_stage<C>(ctx, ctx->stream, d_xyz, n, ctx->cx_xy, ctx->cx_inf, ctx->prefix);
-}
+
+// ---- the one decoded-points front stage -------------------------------------------------------------------------------------
+// Points that arrive in another record than x || y + flag are decoded on the context's stream into ctx->cx_xy / ctx->cx_inf by a first
+// stage — decode_xyz (projective records, xyz_stage) or decode_compressed (x + SEC1 tag records, k_decompress_tagged: one square
+// root per point) —, and the ordinary pipeline `then(d_xy, d_inf)` runs on the result as the second stage of the same call: under
+// KeepStatus, so that it does not clear the first stage's verdicts.  A record that decodes to no point ends the call with
+// ECGPU_ERR_POINT like an off-curve x || y record would.  Both decoders open the call's frame themselves (the lanes are joined and
+// the status word cleared before the decoding kernel); what an empty call does is the caller's business.
 struct KeepStatus {            // the second stage of a two-stage call must not clear the first stage's verdicts
     ecgpu_ctx* ctx;
     explicit KeepStatus(ecgpu_ctx* c) : ctx(c) { ctx->keep_status = true; }
     ~KeepStatus() { ctx->keep_status = false; }
 };
+template <class C>
+int decode_xyz(ecgpu_ctx* ctx, const void* d_xyz, const void* /* no tags */, size_t n) {
+    DevCall front(ctx, 0, {});
+    if (front.rc != ECGPU_OK) return front.rc;
+    return xyz_stage<C>(ctx, ctx->stream, d_xyz, n, ctx->cx_xy, ctx->cx_inf, ctx->prefix);
+}
+template <class C>
+int decode_compressed(ecgpu_ctx* ctx, const void* d_x, const void* d_tag, size_t n) {
+    constexpr int WB = WireBytes<C>::value;
+    DevCall front(ctx, 0, {{ctx->cx_xy, n * 2 * WB + 16}, {ctx->cx_inf, n + 16}});
+    if (front.rc != ECGPU_OK) return front.rc;
+    if (n)
+        launch_decompress_tagged<C>(ctx->stream, (const uint8_t*)d_x, (const uint8_t*)d_tag, n, (uint8_t*)ctx->cx_xy.p,
+                                    (uint8_t*)ctx->cx_inf.p, ctx->d_status);
+    return ECGPU_OK;
+}
+template <class Then>
+int decoded(ecgpu_ctx* ctx, int (*decode)(ecgpu_ctx*, const void*, const void*, size_t), const void* d_points, const void* d_tag,
+            size_t n, Then&& then) {
+    const int rc = decode(ctx, d_points, d_tag, n);
+    if (rc != ECGPU_OK) return rc;
+    KeepStatus keep(ctx);
+    return then(ctx->cx_xy.p, ctx->cx_inf.p);
+}
 
 // The lane the next MSM (or local half of a sharded MSM) of an asynchronous context with ecgpu_set_msm_lanes > 1 goes to: lanes take
 // turns; a lane's stream, events and workspace exist from its first use on.
@@ -827,6 +843,34 @@ int next_lane(ecgpu_ctx* ctx, size_t workspace_bytes, ecgpu_ctx::MsmLane** out) 
     return ECGPU_OK;
 }
 
+// The one way onto a lane.  Everything of this MSM (or local half) runs on the lane's stream and in the lane's buffers, ordered after
+// what the context's stream holds now (the inputs: ev_in) — the conversion of X || Y || Z records too (xyz: into the lane's buffers,
+// beside the previous MSM).  `claim(lane)` is what the caller does to the lane before anything is queued on it, `launch(lane, d_xy,
+// d_inf)` queues its kernels.  Any OTHER entry point called later on this context waits for ev_done first (reset_status): it may
+// read the output or reuse the inputs.  Further MSMs do not — they go to the next lane — and neither does work the caller queues on
+// the stream itself: for that, inputs and outputs belong to the lane until ecgpu_synchronize.  The call's timing marks are the
+// lane's own (ev_a, ev_b: ecgpu_last_timing "accumulate").
+template <class C, class Claim, class Launch>
+int on_lane(ecgpu_ctx* ctx, size_t workspace_bytes, bool xyz, const void* d_xy, const void* d_inf, size_t n, Claim&& claim,
+            Launch&& launch) {
+    int rc;
+    ecgpu_ctx::MsmLane* lp = nullptr;
+    if ((rc = next_lane(ctx, workspace_bytes, &lp)) != ECGPU_OK) return rc;
+    ecgpu_ctx::MsmLane& l = *lp;
+    if ((rc = claim(l)) != ECGPU_OK) return rc;
+    HIP_TRY(ctx, hipEventRecord(l.ev_in, ctx->stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(l.s, l.ev_in, 0));
+    if (xyz) {
+        if ((rc = xyz_stage<C>(ctx, l.s, d_xy, n, l.cx_xy, l.cx_inf, l.prefix)) != ECGPU_OK) return rc;
+        d_xy = l.cx_xy.p;
+        d_inf = l.cx_inf.p;
+    }
+    launch(l, d_xy, d_inf);
+    HIP_TRY(ctx, hipEventRecord(l.ev_done, l.s));
+    ctx->lanes_pending = true;
+    return finish(ctx);
+}
+
 // largest term count for which the per-term multiplication + tree sum replaces the bucket method (0: never);
 // ECGPU_MSM_SMALL_LOG2 overrides the measured default (tuning knob, -1 disables)
 template <class C>
@@ -839,94 +883,59 @@ size_t msm_small_max() {
 }
 
 // xyz: d_xy holds projective records X || Y || Z and d_inf is unused — converted on the MSM's lane when it goes to one, on the
-// context's stream otherwise
+// context's stream otherwise.  (A reducing call: an MSM of no terms goes down the bucket path, which writes the identity.)
 template <class C>
 int msm_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy,
             void* d_out_inf, bool xyz = false) {
-    constexpr int N = C::N, NS = Field<C>::NS;
-    (void)N;
-    int rc;
+    constexpr int NS = Field<C>::NS;
     if (n > msm_max_terms<C>()) {           // sorted entries are sub-term index | sign << 31
         ctx->err = "MSM of 2^31 (k256: 2^30) or more terms: split it and add the partial sums (ecgpu_point_sum)";
         return ECGPU_ERR_ARG;
     }
     const bool small = n >= 1 && n <= msm_small_max<C>() && ctx->msm_c == 0;
-    if (xyz && (small || !(ctx->async && ctx->msm_lanes > 1))) {
-        if ((rc = decode_xyz<C>(ctx, d_xy, n)) != ECGPU_OK) return rc;
-        KeepStatus keep(ctx);
-        return msm_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
-    }
+    const bool lanes = ctx->async && ctx->msm_lanes > 1;
+    if (xyz && (small || !lanes))
+        return decoded(ctx, decode_xyz<C>, d_xy, nullptr, n, [&](const void* xy, const void* inf) {
+            return msm_dev<C>(ctx, d_scalars, xy, inf, n, d_out_xy, d_out_inf);
+        });
     if (small) {
         // Small MSM: the bucket method has a floor of ~1.2 ms of serial work that does not depend on n (running sums, the
         // 240-doubling combine chain).  Below ~2^17 terms one variable-base multiplication per term (all lanes in
         // parallel, ~0.5 ms of latency) and a tree sum of the products are faster.
-        size_t tstride = var_base_slots<C>(n);
-        if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->prefix, ((n + BLOCK - 1) / BLOCK + 1) * 3 * NS * 4)) != ECGPU_OK) return rc;
-        if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-        record(ctx, 0);
+        const size_t tstride = var_base_slots<C>(n);
+        DevCall call(ctx, 0, {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4},
+                              {ctx->prefix, ((n + BLOCK - 1) / BLOCK + 1) * 3 * NS * 4}});
+        if (call.rc != ECGPU_OK) return call.rc;
+        call.mark(0);
         launch_var_base<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n,
                            (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, ctx->d_status);
-        record(ctx, 3);
+        call.mark(3);
         launch_proj_sum<C>(ctx->stream, (uint32_t*)ctx->proj.p, n, (uint32_t*)ctx->prefix.p);
-        record(ctx, 4);
-        record(ctx, 1);
-        if ((rc = normalize_out<C>(ctx, 1, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-        record(ctx, 2);
-        rc = finish(ctx);
-        collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}, {"sort", {0, 3}},
-                             {"accumulate", {3, 4}}, {"reduce", {4, 1}}});
-        return rc;
+        call.mark(4);
+        return call.normalized<C>(1, d_out_xy, d_out_inf, SPANS_MSM);
     }
     MsmPlan plan = msm_plan<C>(n, ctx->msm_c, msm_use_glv<C>(n));
-    if (ctx->async && ctx->msm_lanes > 1) {
-        // one of the lanes: everything of this MSM on the lane's stream and in the lane's buffers, ordered after what the
-        // context's stream holds now (the inputs); its output is ordered by ecgpu_synchronize only
-        ecgpu_ctx::MsmLane* lp = nullptr;
-        if ((rc = next_lane(ctx, plan.workspace_bytes, &lp)) != ECGPU_OK) return rc;
-        ecgpu_ctx::MsmLane& l = *lp;
-        l.parts_out = nullptr;
-        if ((rc = ensure_on(ctx, l.s, l.proj, 3 * NS * 4)) != ECGPU_OK) return rc;
-        if ((rc = ensure_on(ctx, l.s, l.prefix, NS * 4)) != ECGPU_OK) return rc;
-        HIP_TRY(ctx, hipEventRecord(l.ev_in, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(l.s, l.ev_in, 0));
-        if (xyz) {        // the conversion too: on the lane, into the lane's buffers, beside the previous MSM
-            if ((rc = xyz_stage<C>(ctx, l.s, d_xy, n, l.cx_xy, l.cx_inf, l.prefix)) != ECGPU_OK) return rc;
-            d_xy = l.cx_xy.p;
-            d_inf = l.cx_inf.p;
-        }
-        launch_msm<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, l.ws.p, (uint32_t*)l.proj.p,
-                      ctx->d_status, l.ev_a, l.ev_b, (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);   // (the last kernel writes the wire record)
-        // Any OTHER entry point called later on this context waits for this event first (reset_status): it may read the
-        // output or reuse the inputs.  Further MSMs do not — they go to the next lane — and neither does work the caller
-        // queues on the stream itself: for that, inputs and outputs belong to the lane until ecgpu_synchronize.
-        HIP_TRY(ctx, hipEventRecord(l.ev_done, l.s));
-        ctx->lanes_pending = true;
-        return finish(ctx);
-    }
-    if ((rc = ensure(ctx, ctx->proj, 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->msm_ws, plan.workspace_bytes)) != ECGPU_OK) return rc;
+    if (lanes)         // its output is ordered by ecgpu_synchronize only; it is no local half: the lane forgets its parts record
+        return on_lane<C>(ctx, plan.workspace_bytes, xyz, d_xy, d_inf, n, [&](ecgpu_ctx::MsmLane& l) {
+            l.parts_out = nullptr;
+            const int rc = ensure_on(ctx, l.s, l.proj, 3 * NS * 4);
+            return rc != ECGPU_OK ? rc : ensure_on(ctx, l.s, l.prefix, NS * 4);
+        }, [&](ecgpu_ctx::MsmLane& l, const void* xy, const void* inf) {
+            launch_msm<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)xy, (const uint8_t*)inf, n, l.ws.p, (uint32_t*)l.proj.p,
+                          ctx->d_status, l.ev_a, l.ev_b, (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);   // (the last kernel writes the wire record)
+        });
+    DevCall call(ctx, 0, {{ctx->proj, 3 * NS * 4}, {ctx->msm_ws, plan.workspace_bytes}});
+    if (call.rc != ECGPU_OK) return call.rc;
     const bool detail = ctx->timing_on && ctx->ev[6];
     if (detail)
         for (int i = 0; i < 3; i++) plan.detail[i] = ctx->ev[6 + i];
-    record(ctx, 0);
+    call.mark(0);
     launch_msm<C>(plan, ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n,
                   ctx->msm_ws.p, (uint32_t*)ctx->proj.p, ctx->d_status, ctx->timing_on ? ctx->ev[3] : nullptr, ctx->timing_on ? ctx->ev[4] : nullptr, (uint8_t*)d_out_xy,
                   (uint8_t*)d_out_inf);
-    record(ctx, 1);     // (the conversion to affine happens inside the last kernel of the chain: "normalize" is an empty span)
-    record(ctx, 2);
-    rc = finish(ctx);
-    // "accumulate" is the accumulation kernel alone; "reduce" = everything after it = "finish" (bucket finish + running sums) +
-    // "tree" (over the segment sums) + "combine" (window sums, Horner chain, conversion to affine); "sort" = "prepare" + the sort
-    if (detail)
-        collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}, {"sort", {0, 3}}, {"accumulate", {3, 4}},
-                             {"reduce", {4, 1}}, {"prepare", {0, 6}}, {"finish", {4, 7}}, {"tree", {7, 8}}, {"combine", {8, 1}}});
-    else
-        collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}, {"sort", {0, 3}},
-                             {"accumulate", {3, 4}}, {"reduce", {4, 1}}});
-    return rc;
+    call.mark(1);     // (the conversion to affine happens inside the last kernel of the chain: "normalize" is an empty span)
+    call.mark(2);
+    return call.done(detail ? SpanList(SPANS_MSM_DETAIL) : SpanList(SPANS_MSM));
 }
 
 // ---- `LinearCombination::lincomb` in its constant-time form (primeorder/src/projective.rs:484-496 -> :532-557; k256
@@ -938,74 +947,52 @@ template <class C>
 int lincomb_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, void* d_out_xy,
                    void* d_out_inf, bool xyz = false) {
     constexpr int NS = Field<C>::NS, WB = WireBytes<C>::value;
-    int rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    if (n == 0) {                              // the empty sum
+    if (n == 0) {                              // a reducing call: the empty sum is the identity (no secret, no scratch, no marks)
+        DevCall call(ctx, 0, {});
+        if (call.rc != ECGPU_OK) return call.rc;
         HIP_TRY(ctx, hipMemsetAsync(d_out_xy, 0, 2 * WB, ctx->stream));
         if (d_out_inf) HIP_TRY(ctx, hipMemsetAsync(d_out_inf, 1, 1, ctx->stream));
-        return finish(ctx);
+        return call.done_unmarked();
     }
-    CtWipe wipe(ctx, WIPE_SCRATCH);
     const size_t tstride = var_base_slots<C>(n);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->prefix, ((n + BLOCK - 1) / BLOCK + 1) * 3 * NS * 4)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, WIPE_SCRATCH,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}, {ctx->ct_flags, n + 16},
+                  {ctx->prefix, ((n + BLOCK - 1) / BLOCK + 1) * 3 * NS * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     if (xyz)
         launch_xyz_mul_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, n, (uint32_t*)ctx->vtab.p, tstride,
                              (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     else
         launch_var_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n,
                               (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    record(ctx, 3);
+    call.mark(3);
     launch_proj_sum<C>(ctx->stream, (uint32_t*)ctx->proj.p, n, (uint32_t*)ctx->prefix.p);
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, 1, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}, {"accumulate", {0, 3}}, {"reduce", {3, 1}}});
-    return rc;
+    return call.normalized<C>(1, d_out_xy, d_out_inf, SPANS_LINCOMB_CT);
 }
 
-// ---- compressed points into the path: x + SEC1 tag records are decoded on the device (k_decompress_tagged: one square root
-// per point) into the context's scratch, then the ordinary pipeline runs on the x || y records; a record that decodes to no
-// point ends the call with ECGPU_ERR_POINT like an off-curve x || y record would
-template <class C>
-int decode_compressed(ecgpu_ctx* ctx, const void* d_x, const void* d_tag, size_t n) {
-    constexpr int WB = WireBytes<C>::value;
-    int rc;
-    if ((rc = ensure(ctx, ctx->cx_xy, n * 2 * WB + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->cx_inf, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    if (n)
-        launch_decompress_tagged<C>(ctx->stream, (const uint8_t*)d_x, (const uint8_t*)d_tag, n, (uint8_t*)ctx->cx_xy.p,
-                                    (uint8_t*)ctx->cx_inf.p, ctx->d_status);
-    return ECGPU_OK;
-}
+// (the forms over decoded points: an empty ecgpu_batch_mul_xyz_dev returns at once; the other three run their decoder and their
+// pipeline for n == 0 too — the MSM writes the identity, ecgpu_batch_mul_base_and_mul_add_xyz_dev builds the table)
 template <class C>
 int msm_compressed_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_x, const void* d_tag, size_t n, void* d_out_xy,
                        void* d_out_inf) {
-    int rc;
-    if ((rc = decode_compressed<C>(ctx, d_x, d_tag, n)) != ECGPU_OK) return rc;
-    KeepStatus keep(ctx);
-    return msm_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+    return decoded(ctx, decode_compressed<C>, d_x, d_tag, n, [&](const void* xy, const void* inf) {
+        return msm_dev<C>(ctx, d_scalars, xy, inf, n, d_out_xy, d_out_inf);
+    });
 }
 template <class C>
 int mul_var_compressed_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_x, const void* d_tag, size_t n, void* d_out_xy,
                            void* d_out_inf) {
-    int rc;
-    if ((rc = decode_compressed<C>(ctx, d_x, d_tag, n)) != ECGPU_OK) return rc;
-    KeepStatus keep(ctx);
-    return mul_var_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+    return decoded(ctx, decode_compressed<C>, d_x, d_tag, n, [&](const void* xy, const void* inf) {
+        return mul_var_dev<C>(ctx, d_scalars, xy, inf, n, d_out_xy, d_out_inf);
+    });
 }
 template <class C>
 int mul_var_xyz_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xyz, size_t n, void* d_out_xy, void* d_out_inf) {
-    int rc;
     if (n == 0) return ECGPU_OK;
-    if ((rc = decode_xyz<C>(ctx, d_xyz, n)) != ECGPU_OK) return rc;
-    KeepStatus keep(ctx);
-    return mul_var_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+    return decoded(ctx, decode_xyz<C>, d_xyz, nullptr, n, [&](const void* xy, const void* inf) {
+        return mul_var_dev<C>(ctx, d_scalars, xy, inf, n, d_out_xy, d_out_inf);
+    });
 }
 
 // aG + bP per element = two-term lincomb (mul_backend.rs:29-40).  Evaluated as a*G (table kernel) and b*P (variable-base
@@ -1016,31 +1003,24 @@ int mul_add_dev(ecgpu_ctx* ctx, const void* d_a, const void* d_b, const void* d_
     constexpr int NS = Field<C>::NS;
     int rc;
     if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
-    if (n == 0) return (int)ECGPU_OK;
-    size_t tstride = var_base_slots<C>(n);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    const size_t tstride = var_base_slots<C>(n);
+    DevCall call(ctx, 0, {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
     const Table& t = ctx->table[C::ID];
     uint32_t* pa = (uint32_t*)ctx->proj.p;
-    record(ctx, 0);
+    call.mark(0);
     launch_fixed_base<C>(ctx->stream, (const uint8_t*)d_a, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
     launch_var_base<C>(ctx->stream, (const uint8_t*)d_b, (const uint8_t*)d_points_xy, (const uint8_t*)d_points_inf, n,
                        (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);                                   // pa[i] += b[i] P[i]
-    record(ctx, 1);
-    if ((rc = normalize_out<C>(ctx, n, d_out_xy, d_out_inf)) != ECGPU_OK) return rc;
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 template <class C>
 int mul_add_xyz_dev(ecgpu_ctx* ctx, const void* d_a, const void* d_b, const void* d_xyz, size_t n, void* d_out_xy, void* d_out_inf) {
-    int rc;
     if (n == 0) return mul_add_dev<C>(ctx, d_a, d_b, nullptr, nullptr, 0, d_out_xy, d_out_inf);
-    if ((rc = decode_xyz<C>(ctx, d_xyz, n)) != ECGPU_OK) return rc;
-    KeepStatus keep(ctx);
-    return mul_add_dev<C>(ctx, d_a, d_b, ctx->cx_xy.p, ctx->cx_inf.p, n, d_out_xy, d_out_inf);
+    return decoded(ctx, decode_xyz<C>, d_xyz, nullptr, n, [&](const void* xy, const void* inf) {
+        return mul_add_dev<C>(ctx, d_a, d_b, xy, inf, n, d_out_xy, d_out_inf);
+    });
 }
 
 // ---- an MSM whose terms are spread over several GPUs: local half / combining half ------------------------
@@ -1048,7 +1028,6 @@ int mul_add_xyz_dev(ecgpu_ctx* ctx, const void* d_a, const void* d_b, const void
 template <class C>
 int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const void* d_inf, size_t n, size_t plan_terms,
                   void* d_parts, bool xyz = false) {
-    int rc;
     if (n > msm_max_terms<C>() || plan_terms > msm_max_terms<C>()) {
         ctx->err = "MSM shard of 2^31 (k256: 2^30) or more terms";
         return ECGPU_ERR_ARG;
@@ -1057,64 +1036,52 @@ int msm_parts_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_xy, const
         ctx->err = "ecgpu_msm_parts_dev: plan_terms must be at least the shard's term count (and the same on every GPU)";
         return ECGPU_ERR_ARG;
     }
-    if (xyz && !(ctx->async && ctx->msm_lanes > 1)) {
-        if ((rc = decode_xyz<C>(ctx, d_xy, n)) != ECGPU_OK) return rc;
-        KeepStatus keep(ctx);
-        return msm_parts_dev<C>(ctx, d_scalars, ctx->cx_xy.p, ctx->cx_inf.p, n, plan_terms, d_parts);
-    }
+    const bool lanes = ctx->async && ctx->msm_lanes > 1;
+    if (xyz && !lanes)
+        return decoded(ctx, decode_xyz<C>, d_xy, nullptr, n, [&](const void* xy, const void* inf) {
+            return msm_parts_dev<C>(ctx, d_scalars, xy, inf, n, plan_terms, d_parts);
+        });
     const int c = ctx->msm_c ? ctx->msm_c : msm_choose_window<C>(plan_terms);
     MsmPlan plan = msm_plan<C>(n, c, msm_use_glv<C>(plan_terms));
-    if (ctx->async && ctx->msm_lanes > 1) {
-        // Local halves of CONSECUTIVE sharded MSMs on rotating lanes (throughput form): this one runs on its lane's
-        // stream and workspace, ordered after what the context's stream holds now (the inputs), beside the exchange and the
-        // combining half of the previous one, which the caller keeps on the context's stream:
+    if (lanes)
+        // Local halves of CONSECUTIVE sharded MSMs on rotating lanes (throughput form): this one runs on its lane
+        // beside the exchange and the combining half of the previous one, which the caller keeps on the context's stream:
         //     parts(i) -> lane i % L      ecgpu_msm_parts_join_dev(d_parts(i - 1)); all-gather(i - 1); ecgpu_msm_finish_dev(i - 1)
         // d_parts belongs to the lane until ecgpu_msm_parts_join_dev(d_parts) or an ecgpu_msm_finish_dev that reads it (the
         // context's stream then waits for it), or ecgpu_synchronize.
-        ecgpu_ctx::MsmLane* lp = nullptr;
-        if ((rc = next_lane(ctx, plan.workspace_bytes, &lp)) != ECGPU_OK) return rc;
-        ecgpu_ctx::MsmLane& l = *lp;
-        // A lane remembers ONE record.  If the record of its previous local half was never joined (more local halves in flight than
-        // lanes), that half is joined now — the context's stream waits for it before anything queued later —, so that whatever the
-        // caller does with the old record afterwards is still ordered behind the kernels that wrote it.
-        if (l.parts_out) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.ev_done, 0));
-        HIP_TRY(ctx, hipEventRecord(l.ev_in, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(l.s, l.ev_in, 0));
-        if (xyz) {        // the conversion on the lane, into the lane's buffers
-            if ((rc = xyz_stage<C>(ctx, l.s, d_xy, n, l.cx_xy, l.cx_inf, l.prefix)) != ECGPU_OK) return rc;
-            d_xy = l.cx_xy.p;
-            d_inf = l.cx_inf.p;
-        }
-        launch_msm_parts<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, l.ws.p, (uint32_t*)d_parts,
-                            ctx->d_status, l.ev_a, l.ev_b);
-        HIP_TRY(ctx, hipEventRecord(l.ev_done, l.s));
-        l.parts_out = d_parts;
-        ctx->lanes_pending = true;
-        return finish(ctx);
-    }
-    if ((rc = ensure(ctx, ctx->msm_ws, plan.workspace_bytes)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+        return on_lane<C>(ctx, plan.workspace_bytes, xyz, d_xy, d_inf, n, [&](ecgpu_ctx::MsmLane& l) -> int {
+            // A lane remembers ONE record.  If the record of its previous local half was never joined (more local halves in flight
+            // than lanes), that half is joined now — the context's stream waits for it before anything queued later —, so that
+            // whatever the caller does with the old record afterwards is still ordered behind the kernels that wrote it.
+            if (l.parts_out) HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.ev_done, 0));
+            return ECGPU_OK;
+        }, [&](ecgpu_ctx::MsmLane& l, const void* xy, const void* inf) {
+            launch_msm_parts<C>(plan, l.s, (const uint8_t*)d_scalars, (const uint8_t*)xy, (const uint8_t*)inf, n, l.ws.p, (uint32_t*)d_parts,
+                                ctx->d_status, l.ev_a, l.ev_b);
+            l.parts_out = d_parts;
+        });
+    DevCall call(ctx, 0, {{ctx->msm_ws, plan.workspace_bytes}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_msm_parts<C>(plan, ctx->stream, (const uint8_t*)d_scalars, (const uint8_t*)d_xy, (const uint8_t*)d_inf, n, ctx->msm_ws.p,
                         (uint32_t*)d_parts, ctx->d_status, ctx->timing_on ? ctx->ev[3] : nullptr, ctx->timing_on ? ctx->ev[4] : nullptr);
-    record(ctx, 1);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"total", {0, 1}}, {"sort", {0, 3}}, {"accumulate", {3, 4}}, {"reduce", {4, 1}}});
-    return rc;
+    call.mark(1);
+    return call.done(SPANS_MSM_PARTS);
 }
 
 template <class C>
 int msm_finish_dev(ecgpu_ctx* ctx, const void* d_parts_all, int nranks, size_t plan_terms, void* d_out_xy, void* d_out_inf) {
     constexpr int NS = Field<C>::NS;
-    int rc;
     const int c = ctx->msm_c ? ctx->msm_c : msm_choose_window<C>(plan_terms);
     MsmPlan plan = msm_plan<C>(0, c, msm_use_glv<C>(plan_terms));   // only c, nwin and nparts matter here
-    if ((rc = ensure(ctx, ctx->proj, 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->bases, (size_t)plan.nwin * 3 * NS * 4)) != ECGPU_OK) return rc;
     // With local halves in flight on lanes this call does not wait for all of them (that is the point of the lanes), only for those
     // whose record lies inside d_parts_all: the one-rank form passes its own record, and a caller may skip the join when no exchange
-    // of its own reads the record.  Joined records (parts_out cleared) cost nothing here.
-    if (ctx->async && ctx->msm_lanes > 1) {          // (nor does it touch the timing marks: ecgpu_last_timing keeps reading the last lane's)
+    // of its own reads the record.  Joined records (parts_out cleared) cost nothing here.  So this branch stays outside the call
+    // frame, whose first act is to join every lane; nor does it touch the timing marks: ecgpu_last_timing keeps reading the last lane's.
+    if (ctx->async && ctx->msm_lanes > 1) {
+        int rc;
+        if ((rc = ensure(ctx, ctx->proj, 3 * NS * 4)) != ECGPU_OK) return rc;
+        if ((rc = ensure(ctx, ctx->bases, (size_t)plan.nwin * 3 * NS * 4)) != ECGPU_OK) return rc;
         const uintptr_t lo = reinterpret_cast<uintptr_t>(d_parts_all), hi = lo + (size_t)nranks * plan.parts_bytes;
         for (auto& l : ctx->lane) {
             const uintptr_t p = reinterpret_cast<uintptr_t>(l.parts_out);
@@ -1127,15 +1094,14 @@ int msm_finish_dev(ecgpu_ctx* ctx, const void* d_parts_all, int nranks, size_t p
                              (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);
         return finish(ctx);
     }
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-    record(ctx, 0);
+    DevCall call(ctx, 0, {{ctx->proj, 3 * NS * 4}, {ctx->bases, (size_t)plan.nwin * 3 * NS * 4}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
     launch_msm_finish<C>(plan, ctx->stream, (const uint32_t*)d_parts_all, nranks, (uint32_t*)ctx->bases.p, (uint32_t*)ctx->proj.p,
                          (uint8_t*)d_out_xy, (uint8_t*)d_out_inf);
-    record(ctx, 1);
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    call.mark(1);
+    call.mark(2);
+    return call.done();
 }
 
 template <class C>
@@ -1297,6 +1263,26 @@ int curve_error(ecgpu_ctx* ctx, const char* fn) {
     return ECGPU_ERR_CURVE;
 }
 
+// ---- the one argument check of the device-pointer entry points ------------------------------------------------------------
+// An entry point lists its pointers once, each with what is asked of it: NEED = not NULL when n > 0, ALWAYS = not NULL whatever n is
+// (the output of a reducing call, a parts record), OPT = may be NULL; A16 = 16-byte aligned where it is looked at at all (a NEED or
+// OPT pointer when n > 0 and it is there, an ALWAYS pointer always).  In the order of the early returns: no (usable) context ->
+// ECGPU_ERR_ARG without a message; a pointer that fails, or the entry point's own condition on its sizes (`also_bad`) -> arg_error;
+// an operation that does not exist for the curve (`no_such_op`) -> curve_error.  Nothing is queued before this returns ECGPU_OK.
+enum : int { OPT = 0, NEED = 1, ALWAYS = 2, A16 = 4 };
+struct DevArg { const void* p; int how; };
+int dev_args(ecgpu_ctx* ctx, const char* fn, size_t n, std::initializer_list<DevArg> ptrs, bool also_bad = false, bool no_such_op = false) {
+    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
+    bool bad = also_bad;
+    for (const DevArg& a : ptrs) {
+        const bool looked_at = (a.how & ALWAYS) || n;
+        if (!a.p) bad = bad || ((a.how & (NEED | ALWAYS)) && looked_at);
+        else bad = bad || ((a.how & A16) && looked_at && !aligned16(a.p));
+    }
+    if (bad) return arg_error(ctx, fn);
+    return no_such_op ? curve_error(ctx, fn) : (int)ECGPU_OK;
+}
+
 // ---- the one staging path of the host-pointer entry points -------------------------------------------------------------
 // What every such entry point begins with, in the order of its early returns: no (usable) context -> ECGPU_ERR_ARG without a
 // message; the queued work of an asynchronous context drained (SyncScope, which restores the mode when the call ends) -> a
@@ -1420,32 +1406,24 @@ int verify_dev(ecgpu_ctx* ctx, int mode, const void* d_h, const void* d_r, const
     const size_t L = 4 * C::N;
     int rc;
     if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
-    if (n == 0) return (int)ECGPU_OK;
-    size_t tstride = var_base_slots<C>(n);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->vtab, tstride * var_base_tab_words<C>() * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_u1, n * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_u2, n * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_q, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_valid, n + 16)) != ECGPU_OK) return rc;
-    if (mode != VERIFY_RECOVER && (rc = ensure(ctx, ctx->ec_xy, n * 2 * L)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
-    if (mode == VERIFY_SCHNORR_RAW && (rc = ensure(ctx, ctx->ec_r, n * L)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    const size_t tstride = var_base_slots<C>(n);
     // ECDSA verification and recovery invert one scalar per signature: done for the whole batch by Montgomery's trick
     const bool batch_inv = mode == VERIFY_RECOVER || mode == VERIFY_ECDSA;
-    if (batch_inv) {
-        if ((rc = ensure(ctx, ctx->ec_winv, n * L + 16)) != ECGPU_OK) return rc;
-        static_assert(Field<C>::NS >= C::N, "the normalisation's prefix array holds the inverses' prefix products too");
-        if ((rc = ensure(ctx, ctx->prefix, n * Field<C>::NS * 4)) != ECGPU_OK) return rc;      // (the size normalize_out asks for later)
-    }
+    static_assert(Field<C>::NS >= C::N, "the normalisation's prefix array holds the inverses' prefix products too");
+    DevCall call(ctx, 0,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}, {ctx->ec_u1, n * L}, {ctx->ec_u2, n * L},
+                  {ctx->ec_q, n * 2 * L}, {ctx->ec_valid, n + 16}, {ctx->ec_xy, n * 2 * L, mode != VERIFY_RECOVER}, {ctx->ec_inf, n + 16},
+                  {ctx->ec_r, n * L, mode == VERIFY_SCHNORR_RAW}, {ctx->ec_winv, n * L + 16, batch_inv},
+                  {ctx->prefix, n * Field<C>::NS * 4, batch_inv}});      // (the size normalize_out asks for later)
+    if (call.rc != ECGPU_OK) return call.rc;
     uint32_t* inv_prefix = batch_inv ? (uint32_t*)ctx->prefix.p : nullptr;
     uint8_t* inv_out = batch_inv ? (uint8_t*)ctx->ec_winv.p : nullptr;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
     const Table& t = ctx->table[C::ID];
     uint32_t* pa = (uint32_t*)ctx->proj.p;
     uint8_t *u1 = (uint8_t*)ctx->ec_u1.p, *u2 = (uint8_t*)ctx->ec_u2.p, *q = (uint8_t*)ctx->ec_q.p;
     uint8_t* valid = (uint8_t*)ctx->ec_valid.p;
-    record(ctx, 0);
+    call.mark(0);
     if (mode == VERIFY_SCHNORR_RAW) {
         launch_schnorr_prepare_raw(ctx->stream, (const uint8_t*)d_q_xy, (const uint8_t*)d_h, msg_len, (const uint8_t*)d_s, n, u1,
                                    u2, q, (uint8_t*)ctx->ec_r.p, valid);
@@ -1463,10 +1441,10 @@ int verify_dev(ecgpu_ctx* ctx, int mode, const void* d_h, const void* d_r, const
     else
         launch_ecdsa_prepare<C>(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_r, (const uint8_t*)d_s,
                                 (const uint8_t*)d_q_xy, n, reject_high_s, u1, u2, q, valid, inv_prefix, inv_out);
-    record(ctx, 3);
+    call.mark(3);
     launch_fixed_base<C>(ctx->stream, u1, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
     launch_var_base<C>(ctx->stream, u2, q, nullptr, n, (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);   // pa[i] += u2[i] Q[i]
-    record(ctx, 1);
+    call.mark(1);
     if ((rc = normalize_out<C>(ctx, n, mode == VERIFY_RECOVER ? d_out_xy : ctx->ec_xy.p, ctx->ec_inf.p)) != ECGPU_OK) return rc;
     if (mode == VERIFY_RECOVER)
         launch_ecdsa_recover_finish<C>(ctx->stream, (uint8_t*)d_out_xy, (const uint8_t*)ctx->ec_inf.p, valid, n, (uint8_t*)d_ok);
@@ -1482,10 +1460,8 @@ int verify_dev(ecgpu_ctx* ctx, int mode, const void* d_h, const void* d_r, const
     else
         launch_ecdsa_finish<C>(ctx->stream, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, (const uint8_t*)d_r,
                                valid, n, (uint8_t*)d_ok);
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"recode", {0, 3}}, {"main", {3, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    call.mark(2);
+    return call.done(SPANS_VERIFY);
 }
 }  // namespace
 
@@ -1801,44 +1777,38 @@ int ecgpu_last_timing(const ecgpu_ctx* ctx_in, const char* name, double* ms) {
 }
 
 // ---- device-pointer entry points ----
+// Each one is: its pointers, once, with what dev_args checks of them; its `_dev` implementation.
 
 int ecgpu_batch_mul_base_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, size_t n, void* d_out_xy,
                              void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_out_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) { return mul_base_dev<decltype(c)>(ctx, d_scalars, n, d_out_xy, d_out_inf); });
 }
 
 int ecgpu_batch_mul_base_compressed_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, size_t n, void* d_out_x,
                                         void* d_out_tag) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_out_x || !d_out_tag || !aligned16(d_scalars) || !aligned16(d_out_x))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_out_x, NEED | A16}, {d_out_tag, NEED}})) return rc;
     return dispatch(curve, [&](auto c) { return mul_base_dev<decltype(c)>(ctx, d_scalars, n, d_out_x, d_out_tag, true); });
 }
 
 int ecgpu_batch_mul_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy,
                         const void* d_points_inf, size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_points_xy || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xy) ||
-              !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT},
+                                             {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return mul_var_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
 }
 
 int ecgpu_batch_mul_base_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_out_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) { return mul_base_ct_dev<decltype(c)>(ctx, d_scalars, n, d_out_xy, d_out_inf); });
 }
 
 int ecgpu_batch_mul_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, const void* d_points_inf,
                            size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_points_xy || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xy) ||
-              !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT},
+                                             {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return mul_var_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
@@ -1846,9 +1816,8 @@ int ecgpu_batch_mul_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, con
 
 int ecgpu_batch_mul_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
                                void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_points_xyz || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xyz) || !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xyz, NEED | A16}, {d_out_xy, NEED | A16}, {d_out_inf, OPT}}))
+        return rc;
     return dispatch(curve, [&](auto c) {
         return mul_var_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
     });
@@ -1856,9 +1825,8 @@ int ecgpu_batch_mul_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars,
 
 int ecgpu_msm_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, const void* d_points_inf,
                   size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xy || !aligned16(d_scalars) || !aligned16(d_points_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT},
+                                             {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return msm_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
@@ -1866,9 +1834,8 @@ int ecgpu_msm_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* 
 
 int ecgpu_lincomb_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, const void* d_points_inf,
                          size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xy || !aligned16(d_scalars) || !aligned16(d_points_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT},
+                                             {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return lincomb_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
@@ -1876,9 +1843,8 @@ int ecgpu_lincomb_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const
 
 int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
                              void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xyz, NEED | A16}, {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}}))
+        return rc;
     return dispatch(curve, [&](auto c) {
         return lincomb_ct_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
     });
@@ -1886,17 +1852,15 @@ int ecgpu_lincomb_ct_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, c
 
 int ecgpu_batch_mul_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
                             void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_points_xyz || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_xyz) || !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xyz, NEED | A16}, {d_out_xy, NEED | A16}, {d_out_inf, OPT}}))
+        return rc;
     return dispatch(curve, [&](auto c) { return mul_var_xyz_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, n, d_out_xy, d_out_inf); });
 }
 
 int ecgpu_msm_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, void* d_out_xy,
                       void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xyz, NEED | A16}, {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}}))
+        return rc;
     return dispatch(curve, [&](auto c) {
         return msm_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, d_out_xy, d_out_inf, true);
     });
@@ -1904,10 +1868,8 @@ int ecgpu_msm_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const vo
 
 int ecgpu_msm_compressed_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_x, const void* d_points_tag,
                              size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_x || !d_points_tag || !aligned16(d_scalars) || !aligned16(d_points_x)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_x, NEED | A16}, {d_points_tag, NEED},
+                                             {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return msm_compressed_dev<decltype(c)>(ctx, d_scalars, d_points_x, d_points_tag, n, d_out_xy, d_out_inf);
     });
@@ -1915,10 +1877,8 @@ int ecgpu_msm_compressed_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, c
 
 int ecgpu_batch_mul_compressed_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_x,
                                    const void* d_points_tag, size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_scalars || !d_points_x || !d_points_tag || !d_out_xy || !aligned16(d_scalars) || !aligned16(d_points_x) ||
-              !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_x, NEED | A16}, {d_points_tag, NEED},
+                                             {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return mul_var_compressed_dev<decltype(c)>(ctx, d_scalars, d_points_x, d_points_tag, n, d_out_xy, d_out_inf);
     });
@@ -1946,9 +1906,8 @@ int ecgpu_msm_plan_window(ecgpu_ctx* ctx, int curve, size_t plan_terms) {
 
 int ecgpu_msm_parts_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, const void* d_points_inf,
                         size_t n, size_t plan_terms, void* d_parts) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_parts || !aligned16(d_parts)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xy || !aligned16(d_scalars) || !aligned16(d_points_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT}, {d_parts, ALWAYS | A16}}))
+        return rc;
     return dispatch(curve, [&](auto c) {
         return msm_parts_dev<decltype(c)>(ctx, d_scalars, d_points_xy, d_points_inf, n, plan_terms, d_parts);
     });
@@ -1956,17 +1915,14 @@ int ecgpu_msm_parts_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const 
 
 int ecgpu_msm_parts_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xyz, size_t n, size_t plan_terms,
                             void* d_parts) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_parts || !aligned16(d_parts)) return arg_error(ctx, __func__);
-    if (n && (!d_scalars || !d_points_xyz || !aligned16(d_scalars) || !aligned16(d_points_xyz))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_scalars, NEED | A16}, {d_points_xyz, NEED | A16}, {d_parts, ALWAYS | A16}})) return rc;
     return dispatch(curve, [&](auto c) {
         return msm_parts_dev<decltype(c)>(ctx, d_scalars, d_points_xyz, nullptr, n, plan_terms, d_parts, true);
     });
 }
 
 int ecgpu_msm_parts_join_dev(ecgpu_ctx* ctx, const void* d_parts) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_parts) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, 0, {{d_parts, ALWAYS}})) return rc;
     for (auto& l : ctx->lane)
         if (l.s && l.ev_done && l.parts_out == d_parts) {
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, l.ev_done, 0));
@@ -1977,9 +1933,8 @@ int ecgpu_msm_parts_join_dev(ecgpu_ctx* ctx, const void* d_parts) {
 
 int ecgpu_msm_finish_dev(ecgpu_ctx* ctx, int curve, const void* d_parts_all, int nranks, size_t plan_terms, void* d_out_xy,
                          void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_parts_all || !aligned16(d_parts_all) || !d_out_xy || !aligned16(d_out_xy) || nranks < 1 || nranks > 4096)
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, 0, {{d_parts_all, ALWAYS | A16}, {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}},
+                          nranks < 1 || nranks > 4096)) return rc;
     return dispatch(curve, [&](auto c) {
         return msm_finish_dev<decltype(c)>(ctx, d_parts_all, nranks, plan_terms, d_out_xy, d_out_inf);
     });
@@ -1987,15 +1942,14 @@ int ecgpu_msm_finish_dev(ecgpu_ctx* ctx, int curve, const void* d_parts_all, int
 
 int ecgpu_batch_normalize_dev(ecgpu_ctx* ctx, int curve, const void* d_points_xyz, size_t n, void* d_out_xy,
                               void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_points_xyz || !d_out_xy || !aligned16(d_points_xyz) || !aligned16(d_out_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_points_xyz, NEED | A16}, {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) { return normalize_dev<decltype(c)>(ctx, d_points_xyz, n, d_out_xy, d_out_inf); });
 }
 
 int ecgpu_point_sum_dev(ecgpu_ctx* ctx, int curve, const void* d_points_xy, const void* d_points_inf, size_t n,
                         void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (!d_out_xy || !aligned16(d_out_xy) || (n && (!d_points_xy || !aligned16(d_points_xy)))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_points_xy, NEED | A16}, {d_points_inf, OPT}, {d_out_xy, ALWAYS | A16}, {d_out_inf, OPT}}))
+        return rc;
     return dispatch(curve, [&](auto c) {
         return point_sum_dev<decltype(c)>(ctx, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
@@ -2004,11 +1958,8 @@ int ecgpu_point_sum_dev(ecgpu_ctx* ctx, int curve, const void* d_points_xy, cons
 int ecgpu_batch_mul_base_and_mul_add_dev(ecgpu_ctx* ctx, int curve, const void* d_a, const void* d_b,
                                          const void* d_points_xy, const void* d_points_inf, size_t n, void* d_out_xy,
                                          void* d_out_inf) {
-    // (mul_add_dev)
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_a || !d_b || !d_points_xy || !d_out_xy || !aligned16(d_a) || !aligned16(d_b) ||
-              !aligned16(d_points_xy) || !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_a, NEED | A16}, {d_b, NEED | A16}, {d_points_xy, NEED | A16}, {d_points_inf, OPT},
+                                             {d_out_xy, NEED | A16}, {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return mul_add_dev<decltype(c)>(ctx, d_a, d_b, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf);
     });
@@ -2016,47 +1967,46 @@ int ecgpu_batch_mul_base_and_mul_add_dev(ecgpu_ctx* ctx, int curve, const void* 
 
 int ecgpu_batch_mul_base_and_mul_add_xyz_dev(ecgpu_ctx* ctx, int curve, const void* d_a, const void* d_b, const void* d_points_xyz,
                                              size_t n, void* d_out_xy, void* d_out_inf) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_a || !d_b || !d_points_xyz || !d_out_xy || !aligned16(d_a) || !aligned16(d_b) || !aligned16(d_points_xyz) ||
-              !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_a, NEED | A16}, {d_b, NEED | A16}, {d_points_xyz, NEED | A16}, {d_out_xy, NEED | A16},
+                                             {d_out_inf, OPT}})) return rc;
     return dispatch(curve, [&](auto c) {
         return mul_add_xyz_dev<decltype(c)>(ctx, d_a, d_b, d_points_xyz, n, d_out_xy, d_out_inf);
     });
+}
+
+// sm2 signatures are SM2DSA (sm2/src/dsa.rs), bign's its own scheme (bignp256/src/ecdsa.rs) — not ECDSA; p192 has no
+// `DigestAlgorithm` (p192/src/ecdsa.rs), so the forms that hash a message do not exist for it
+inline bool not_ecdsa(int curve, bool hashes = false) {
+    return curve == ECGPU_SM2 || curve == ECGPU_BIGN256 || (hashes && curve == ECGPU_P192);
 }
 
 int ecgpu_ecdsa_verify_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_z, const void* d_r, const void* d_s,
                                  const void* d_q_xy, size_t n, int reject_high_s, void* d_ok) {
     // per element: u1 = z/s, u2 = r/s (mod n), R = u1 G + u2 Q (the kernels of ecgpu_batch_mul_base_and_mul_add),
     // ok = x(R) mod n == r.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_z || !d_r || !d_s || !d_q_xy || !d_ok || !aligned16(d_z) || !aligned16(d_r) || !aligned16(d_s) ||
-              !aligned16(d_q_xy)))
-        return arg_error(ctx, __func__);
-    if (curve == ECGPU_SM2 || curve == ECGPU_BIGN256)          // sm2 signatures are SM2DSA (sm2/src/dsa.rs), bign's its own scheme
-        return curve_error(ctx, __func__);                     // (bignp256/src/ecdsa.rs) — not ECDSA
+    if (int rc = dev_args(ctx, __func__, n, {{d_z, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}},
+                          false, not_ecdsa(curve))) return rc;
     return dispatch(curve, [&](auto c) {
         return verify_dev<decltype(c)>(ctx, VERIFY_ECDSA, d_z, d_r, d_s, d_q_xy, n, reject_high_s, d_ok);
     });
 }
 
+// (the three message-level verifiers: the hash kernel is a front stage of the call — the frame is opened before it, so the MSM
+// lanes are joined before it reads the caller's messages, and verify_dev runs as the second stage, under KeepStatus)
 int ecgpu_ecdsa_verify_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_q_xy, const void* d_msgs, size_t msg_len,
                                      const void* d_sigs, size_t n, int reject_high_s, void* d_ok) {
     // Verifier::verify(msg, sig): the curve's digest on the device, z = bits2field(digest), then the prehash path.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_q_xy || !d_sigs || !d_ok || (msg_len && !d_msgs) || !aligned16(d_q_xy) || !aligned16(d_sigs))) return arg_error(ctx, __func__);
-    if (curve == ECGPU_SM2 || curve == ECGPU_BIGN256 || curve == ECGPU_P192)   // not ECDSA curves; p192 has no `DigestAlgorithm` (p192/src/ecdsa.rs)
-        return curve_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_q_xy, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_sigs, NEED | A16}, {d_ok, NEED}},
+                          false, not_ecdsa(curve, true))) return rc;
     return dispatch(curve, [&](auto c) {
         using C = decltype(c);
         if (n == 0) return (int)ECGPU_OK;
         const size_t L = WireBytes<C>::value;
-        int rc;
-        if ((rc = ensure(ctx, ctx->ec_e, n * L + 16)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->ec_r, n * L + 16)) != ECGPU_OK) return rc;
-        if ((rc = ensure(ctx, ctx->ec_s, n * L + 16)) != ECGPU_OK) return rc;
+        DevCall front(ctx, 0, {{ctx->ec_e, n * L + 16}, {ctx->ec_r, n * L + 16}, {ctx->ec_s, n * L + 16}});
+        if (front.rc != ECGPU_OK) return front.rc;
         launch_ecdsa_hash_msg<C>(ctx->stream, (const uint8_t*)d_msgs, msg_len, (const uint8_t*)d_sigs, n, (uint8_t*)ctx->ec_e.p,
                                  (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
+        KeepStatus keep(ctx);
         return verify_dev<C>(ctx, VERIFY_ECDSA, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, reject_high_s, d_ok);
     });
 }
@@ -2064,12 +2014,8 @@ int ecgpu_ecdsa_verify_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_q_
 int ecgpu_ecdsa_recover_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_z, const void* d_r, const void* d_s,
                                   const void* d_recid, size_t n, int reject_high_s, void* d_out_xy, void* d_ok) {
     // per element: R = decompress(r or r + n, parity), key = -(z/r) G + (s/r) R.  See ecgpu_ecdsa.h / ecgpu_verify.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_z || !d_r || !d_s || !d_recid || !d_out_xy || !d_ok || !aligned16(d_z) || !aligned16(d_r) || !aligned16(d_s) ||
-              !aligned16(d_out_xy)))
-        return arg_error(ctx, __func__);
-    if (curve == ECGPU_SM2 || curve == ECGPU_BIGN256)   // not ECDSA curves
-        return curve_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_z, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_recid, NEED},
+                                             {d_out_xy, NEED | A16}, {d_ok, NEED}}, false, not_ecdsa(curve))) return rc;
     return dispatch(curve, [&](auto c) {
         return verify_dev<decltype(c)>(ctx, VERIFY_RECOVER, d_z, d_r, d_s, d_recid, n, reject_high_s, d_ok, 0, d_out_xy);
     });
@@ -2078,80 +2024,67 @@ int ecgpu_ecdsa_recover_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_z, co
 int ecgpu_sm2dsa_verify_batch_dev(ecgpu_ctx* ctx, const void* d_e, const void* d_r, const void* d_s, const void* d_q_xy, size_t n,
                                   void* d_ok) {
     // SM2DSA on the prehash: t = r + s, (x1, y1) = s G + t Q, ok = (e + x1 mod n == r).  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_e || !d_r || !d_s || !d_q_xy || !d_ok || !aligned16(d_e) || !aligned16(d_r) || !aligned16(d_s) ||
-              !aligned16(d_q_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_e, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}}))
+        return rc;
     return verify_dev<Sm2Params>(ctx, VERIFY_SM2DSA, d_e, d_r, d_s, d_q_xy, n, 0, d_ok);
 }
 
 int ecgpu_sm2dsa_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_distid, size_t distid_len, const void* d_q_xy, const void* d_msgs,
                                       size_t msg_len, const void* d_sigs, size_t n, void* d_ok) {
     // VerifyingKey::new(distid, Q)?.verify(msg, sig): Z and e = SM3(Z || M) on the device, then the prehash path.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (distid_len > 8191 || (n && (!d_q_xy || !d_sigs || !d_ok || (msg_len && !d_msgs) || (distid_len && !d_distid) || !aligned16(d_q_xy) ||
-                                    !aligned16(d_sigs))))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_distid, distid_len ? NEED : OPT}, {d_q_xy, NEED | A16}, {d_msgs, msg_len ? NEED : OPT},
+                                             {d_sigs, NEED | A16}, {d_ok, NEED}}, distid_len > 8191)) return rc;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = ensure(ctx, ctx->ec_e, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_r, n * 32)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_s, n * 32)) != ECGPU_OK) return rc;
+    DevCall front(ctx, 0, {{ctx->ec_e, n * 32}, {ctx->ec_r, n * 32}, {ctx->ec_s, n * 32}});
+    if (front.rc != ECGPU_OK) return front.rc;
     launch_sm2dsa_hash_msg(ctx->stream, (const uint8_t*)d_distid, distid_len, (const uint8_t*)d_q_xy, (const uint8_t*)d_msgs, msg_len,
                            (const uint8_t*)d_sigs, n, (uint8_t*)ctx->ec_e.p, (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
+    KeepStatus keep(ctx);
     return verify_dev<Sm2Params>(ctx, VERIFY_SM2DSA, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, 0, d_ok);
 }
 
 int ecgpu_bign_verify_batch_dev(ecgpu_ctx* ctx, const void* d_h, const void* d_sigs, const void* d_q_xy, size_t n, void* d_ok) {
     // bign on the prehash: R = ((S1 + H) mod q) G + (S0 + 2^128) Q, ok = (S0 == belt-hash(OID || x(R) || H)[..16]).  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_h || !d_sigs || !d_q_xy || !d_ok || !aligned16(d_h) || !aligned16(d_sigs) || !aligned16(d_q_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_h, NEED | A16}, {d_sigs, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}})) return rc;
     return verify_dev<Bign256Params>(ctx, VERIFY_BIGN, d_h, nullptr, d_sigs, d_q_xy, n, 0, d_ok);
 }
 
 int ecgpu_bign_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_q_xy, const void* d_msgs, size_t msg_len, const void* d_sigs, size_t n,
                                     void* d_ok) {
     // VerifyingKey::verify(msg, sig): H = belt-hash(msg) on the device, then the prehash path.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_q_xy || !d_sigs || !d_ok || (msg_len && !d_msgs) || !aligned16(d_q_xy) || !aligned16(d_sigs)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_q_xy, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_sigs, NEED | A16}, {d_ok, NEED}}))
+        return rc;
     if (n == 0) return ECGPU_OK;
-    int rc;
-    if ((rc = ensure(ctx, ctx->ec_e, n * 32)) != ECGPU_OK) return rc;
+    DevCall front(ctx, 0, {{ctx->ec_e, n * 32}});
+    if (front.rc != ECGPU_OK) return front.rc;
     launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)ctx->ec_e.p);
+    KeepStatus keep(ctx);
     return verify_dev<Bign256Params>(ctx, VERIFY_BIGN, ctx->ec_e.p, nullptr, d_sigs, d_q_xy, n, 0, d_ok);
 }
 
 int ecgpu_schnorr_verify_batch_dev(ecgpu_ctx* ctx, const void* d_e, const void* d_r, const void* d_s, const void* d_p_xy,
                                    size_t n, void* d_ok) {
     // BIP340 over secp256k1: R = s G - e P, ok = R finite, y(R) even, x(R) == r.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_e || !d_r || !d_s || !d_p_xy || !d_ok || !aligned16(d_e) || !aligned16(d_r) || !aligned16(d_s) ||
-              !aligned16(d_p_xy)))
-        return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_e, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_p_xy, NEED | A16}, {d_ok, NEED}}))
+        return rc;
     return verify_dev<K256Params>(ctx, VERIFY_SCHNORR, d_e, d_r, d_s, d_p_xy, n, 0, d_ok);
 }
 
 int ecgpu_schnorr_verify_raw_batch_dev(ecgpu_ctx* ctx, const void* d_pk_x, const void* d_msgs, size_t msg_len, const void* d_sigs,
                                        size_t n, void* d_ok) {
     // VerifyingKey::from_bytes(pk)?.verify_raw(msg, sig) from wire bytes: lift_x, challenge hash, s G - e P.  See ecgpu_ecdsa.h.
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_pk_x || !d_sigs || !d_ok || (msg_len && !d_msgs) || !aligned16(d_pk_x) || !aligned16(d_sigs))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_pk_x, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_sigs, NEED | A16}, {d_ok, NEED}}))
+        return rc;
     return verify_dev<K256Params>(ctx, VERIFY_SCHNORR_RAW, d_msgs, nullptr, d_sigs, d_pk_x, n, 0, d_ok, msg_len);
 }
 
 // ---- signing (ecgpu_sign.h): the entry points around ecdsa_sign_dev ----
-// every argument is checked before anything is queued.  from_msg: d_z is the message array (NULL allowed when msg_len == 0)
+// every argument is checked before anything is queued.  from_msg: d_z is the message array (NULL allowed when msg_len == 0); a
+// nonce array is alignment-checked whenever there is one
 static int ecdsa_sign_entry(ecgpu_ctx* ctx, const char* fn, int curve, bool rfc6979, const void* d_d, const void* d_k, const void* d_z,
                             size_t n, int normalize_s, void* d_sig, void* d_recid, void* d_ok, bool from_msg = false, size_t msg_len = 0) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    const bool z_bad = from_msg ? (msg_len && !d_z) : (!d_z || !aligned16(d_z));
-    if (n && (!d_d || (!rfc6979 && !d_k) || z_bad || !d_sig || !d_recid || !d_ok || !aligned16(d_d) || (d_k && !aligned16(d_k)) ||
-              !aligned16(d_sig)))
-        return arg_error(ctx, fn);
-    if (curve == ECGPU_SM2 || curve == ECGPU_BIGN256 || (rfc6979 && curve == ECGPU_P192))   // not ECDSA; p192 has no `DigestAlgorithm`
-        return curve_error(ctx, fn);
+    if (int rc = dev_args(ctx, fn, n, {{d_d, NEED | A16}, {d_k, (rfc6979 ? OPT : NEED) | A16}, {d_z, from_msg ? (msg_len ? NEED : OPT) : NEED | A16},
+                                       {d_sig, NEED | A16}, {d_recid, NEED}, {d_ok, NEED}}, false, not_ecdsa(curve, rfc6979))) return rc;
     const int rc = dispatch(curve, [&](auto c) {
         return ecdsa_sign_dev<decltype(c)>(ctx, d_d, rfc6979 ? nullptr : d_k, d_z, n, normalize_s, d_sig, d_recid, d_ok, from_msg, msg_len);
     });
@@ -2181,49 +2114,38 @@ int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx* ctx, const void* d_sk, const voi
     // `SigningKey::sign_raw(msg, aux_rand)` with the key fix-up: P = d G, the nonce hashes, R = k G, s = k + e d.  See ecgpu_sign.h.
     using C = K256Params;
     constexpr int NS = Field<C>::NS;
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_sk || !d_aux_rand || !d_out_sig || !d_ok || (msg_len && !d_msgs) || !aligned16(d_sk) || !aligned16(d_aux_rand) ||
-              !aligned16(d_out_sig)))
-        return arg_error(ctx, __func__);
     int rc;
+    if ((rc = dev_args(ctx, __func__, n, {{d_sk, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_aux_rand, NEED | A16}, {d_out_sig, NEED | A16},
+                                          {d_ok, NEED}})) != ECGPU_OK) return rc;
     if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
-    CtWipe wipe(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN);
-    if ((rc = ensure(ctx, ctx->proj, n * 3 * NS * 4)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ct_flags, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->sg_k, n * 32 + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->sg_flag, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->sg_dp, n * 64 + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_xy, n * 64 + 16)) != ECGPU_OK) return rc;
-    if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
-    if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
+                  {ctx->sg_dp, n * 64 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}});
+    if (call.rc != ECGPU_OK) return call.rc;
     uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *dp = (uint8_t*)ctx->sg_dp.p;
     uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
     const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
-    record(ctx, 0);
+    call.mark(0);
     launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_sk, n, k, flag);                   // d, or 1 in place of an unusable key
     launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
     if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // P = d G
     launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n, dp, k, flag);
     launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    record(ctx, 1);
+    call.mark(1);
     if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
     launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
-    record(ctx, 2);
-    rc = finish(ctx);
-    collect_timing(ctx, {{"main", {0, 1}}, {"normalize", {1, 2}}, {"total", {0, 2}}});
-    return rc;
+    call.mark(2);
+    return call.done();
 }
 
 static int ecdh_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, size_t n, void* d_out_x, void* d_ok,
                     bool ct) {
     // SharedSecret_i = x(k_i * P_i): the variable-base kernel (ct: its uniform-schedule form), normalisation into scratch,
-    // x extraction
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_out_x || !d_ok || !aligned16(d_out_x))) return arg_error(ctx, __func__);
-    size_t L = ecgpu_field_bytes(curve);
-    if (!L) return curve_error(ctx, __func__);
+    // x extraction.  (The inputs are checked by the batch multiplication's own entry point below.)
     int rc;
+    if ((rc = dev_args(ctx, __func__, n, {{d_out_x, NEED | A16}, {d_ok, NEED}}, false, !ecgpu_field_bytes(curve))) != ECGPU_OK) return rc;
+    const size_t L = ecgpu_field_bytes(curve);
     CtWipe wipe(ctx, ct ? WIPE_EC : 0);             // (declared first: runs after the x extraction below has been queued)
     if ((rc = ensure(ctx, ctx->ec_xy, n * 2 * L + 16)) != ECGPU_OK) return rc;
     if ((rc = ensure(ctx, ctx->ec_inf, n + 16)) != ECGPU_OK) return rc;
@@ -2251,19 +2173,16 @@ int ecgpu_batch_ecdh_ct_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, co
 
 int ecgpu_batch_decompress_dev(ecgpu_ctx* ctx, int curve, const void* d_xs, const void* d_y_is_odd, size_t n, void* d_out_xy,
                                void* d_ok) {
-    if (!check_ctx(ctx)) return ECGPU_ERR_ARG;
-    if (n && (!d_xs || !d_y_is_odd || !d_out_xy || !d_ok || !aligned16(d_xs) || !aligned16(d_out_xy))) return arg_error(ctx, __func__);
+    if (int rc = dev_args(ctx, __func__, n, {{d_xs, NEED | A16}, {d_y_is_odd, NEED}, {d_out_xy, NEED | A16}, {d_ok, NEED}})) return rc;
     return dispatch(curve, [&](auto c) {
         using C = decltype(c);
         if (n == 0) return (int)ECGPU_OK;
-        int rc;
-        if ((rc = reset_status(ctx)) != ECGPU_OK) return rc;
-        record(ctx, 0);
+        DevCall call(ctx, 0, {});
+        if (call.rc != ECGPU_OK) return call.rc;
+        call.mark(0);
         launch_decompress<C>(ctx->stream, (const uint8_t*)d_xs, (const uint8_t*)d_y_is_odd, n, (uint8_t*)d_out_xy, (uint8_t*)d_ok);
-        record(ctx, 1);
-        rc = finish(ctx);
-        collect_timing(ctx, {{"main", {0, 1}}, {"total", {0, 1}}});
-        return rc;
+        call.mark(1);
+        return call.done(SPANS_NO_NORMALIZE);
     });
 }
 
