@@ -24,10 +24,6 @@
 
 using namespace ecgpu;
 
-#ifndef ECGPU_FIXED_SOA_DEFAULT
-#define ECGPU_FIXED_SOA_DEFAULT true
-#endif
-
 namespace {
 
 constexpr int BLOCK = 256;
@@ -597,13 +593,6 @@ int normalize_out(ecgpu_ctx* ctx, size_t n, void* d_out_xy, void* d_out_inf, boo
     return ECGPU_OK;
 }
 
-// The hand-over between k_fixed_base and k_normalize quad-major (store_proj_soa, ecgpu_kernels.h: a wave's load or store is 1,024
-// contiguous bytes instead of 64 pieces 144 bytes apart)?  A/B: ECGPU_FIXED_SOA = 0 / 1 in the tool build (profiles/r06/).
-inline bool fixed_soa() {
-    if (const char* e = knob("ECGPU_FIXED_SOA")) return e[0] != '0';
-    return ECGPU_FIXED_SOA_DEFAULT;
-}
-
 // ---- device-pointer implementations --------------------------------------------------------------------
 
 // The one call frame of the device-pointer pipelines (the counterpart of HostCall / staged below).  An implementation states
@@ -651,7 +640,10 @@ int mul_base_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out_xy
     DevCall call(ctx, 0, {{ctx->proj, n * 3 * NS * 4}});
     if (call.rc != ECGPU_OK) return call.rc;
     const Table& t = ctx->table[C::ID];
-    const bool soa = !compressed && fixed_soa();
+    // The hand-over between k_fixed_base and k_normalize is quad-major (store_proj_soa, ecgpu_kernels.h: a wave's load or store is
+    // 1,024 contiguous bytes instead of 64 pieces 144 bytes apart; profiles/r06/fixed_soa_handover_ab.txt); the compressed form's
+    // own normalisation reads the record-major one.
+    const bool soa = !compressed;
     call.mark(0);
     launch_fixed_base<C>(ctx->stream, (const uint8_t*)d_scalars, n, (const uint32_t*)t.d, t.w, t.nwin, (uint32_t*)ctx->proj.p,
                          ctx->d_status, soa);

@@ -207,22 +207,20 @@ ECGPU_HD Proj<C> ct_dbl4(const Proj<C>& acc, const Fe<C::NL>& b) {
     }
 }
 
-// The four doublings AND the table scan for the digit that follows them, interleaved (round 5): the reads of entries 2s + 1, 2s + 2
+// The four doublings AND the table scan for the digit that follows them, interleaved: the reads of entries 2s + 1, 2s + 2
 // are issued in front of doubling s and selected behind it, so that they fly under ~850 multiply-adds instead of being waited
 // for in a loop of their own between the doublings and the addition (the stand-alone scan's waits were what the second wave per
 // SIMD had to cover: 84 % of the kernel's cycles issued an instruction against 89 % for the variable-time ladder).  The same
 // entries, masks and selections in the same order for every input: nothing for tools/ct_isa_check.py to object to.  Costs the
-// registers of two entries in flight across a doubling (2 x 3 NL) and of the selection (3 NL H): used where that fits (NL <= 10).
-#ifndef ECGPU_CT_SCAN_UNDER_DBL
-#define ECGPU_CT_SCAN_UNDER_DBL 1
-#endif
+// registers of two entries in flight across a doubling (2 x 3 NL) and of the selection (3 NL H): used where that fits (NL <= 10;
+// profiles/r05/ct_scan_under_doublings_ab.txt).
 #if defined(__HIP_DEVICE_COMPILE__)
 #define ECGPU_CT_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define ECGPU_CT_SCHED_FENCE() ((void)0)
 #endif
 template <class C>
-constexpr bool ct_scan_under_dbl() { return ECGPU_CT_SCAN_UNDER_DBL && C::NL <= 10; }
+constexpr bool ct_scan_under_dbl() { return C::NL <= 10; }
 
 template <class C, class TabIO, int H>
 ECGPU_HD Proj<C> ct_dbl4_scan(const Proj<C>& acc, const Fe<C::NL>& b, const TabIO& tab, const uint32_t* xabs, Proj<C>* t) {

@@ -6,7 +6,7 @@
 // `make -C elliptic-curves_amd` also links lib/libecgpu_knobs.so — the same objects, with the one translation unit that
 // defines knob() (ecgpu_misc.hip) compiled -DECGPU_TUNING_KNOBS=1, where it is getenv — for tools/gpu_msm_*.py, the `env:`
 // recipe of tools/gpu_run.sh, tools/gpu_fuzz.py and the few tests that force a code path (two-level sort at small n, chunk
-// sizes, the chunked host-pointer MSM, the fused tail): they load it through ECGPU_TOOL_LIB / Engine(..., variant="knobs").
+// sizes, the chunked host-pointer MSM): they load it through ECGPU_TOOL_LIB / Engine(..., variant="knobs").
 // Ranges are validated where a knob is read; results never depend on one.
 #pragma once
 

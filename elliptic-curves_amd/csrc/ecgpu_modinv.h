@@ -21,11 +21,6 @@
 
 #include "ecgpu_params.h"
 
-// -DECGPU_DIVSTEPS_MAD=0: the division steps with masks and additions as until round 5 (A/B: profiles/r06/)
-#ifndef ECGPU_DIVSTEPS_MAD
-#define ECGPU_DIVSTEPS_MAD 1
-#endif
-
 namespace ecgpu {
 
 template <int NW>          // modulus size in 32-bit words: 6, 7, 8, 12 or 17
@@ -76,11 +71,12 @@ struct ModInv {
 
     // 30 half-delta division steps on the low bits; zeta = -(delta + 1/2)
     //
-    // Round 6: the conditional additions of a step as MULTIPLY-ADDS by a multiplier in {-1, 0, +1} resp. {0, 1} — g += (+-f) & c2 is
+    // The conditional additions of a step are MULTIPLY-ADDS by a multiplier in {-1, 0, +1} resp. {0, 1} — g += (+-f) & c2 is
     // g += f * m1 with m1 = sign(zeta) restricted to "g odd", f += g & c1 is f += g * m2 — on 64-bit accumulators whose upper halves are
     // never read (the product of a 32-bit value by 0xFFFFFFFF is its negative modulo 2^32: only the lower half of a pair carries the
-    // value, the carry into the upper half is garbage and stays there).  One v_mad_u64_u32 replaces xor + sub + and + add: 16
-    // instructions per step instead of 23 (ISA of k_normalize<K256Params, 0>, tools/isa_loops.py).  A division-step inversion is a lone
+    // value, the carry into the upper half is garbage and stays there).  One v_mad_u64_u32 replaces the xor + sub + and + add of a
+    // step written with masks and additions: 16 instructions per step instead of 23 (ISA of k_normalize<K256Params, 0>,
+    // tools/isa_loops.py; measured: profiles/r06/divsteps_mad_ab.txt).  A division-step inversion is a lone
     // wave's instruction COUNT wherever it matters (k_normalize, k_msm_combine, k_scalar_batch_inv: one wave per SIMD issues an
     // instruction every ~7 cycles whatever it is), so the six full-rate multiply-adds cost nothing there; where the SIMD is shared
     // (the table build of the ladders) six 4-cycle and ten 2-cycle instructions replace twenty-three 2-cycle ones: equal.
@@ -126,7 +122,6 @@ struct ModInv {
 #endif
     }
     static ECGPU_HD int32_t divsteps_30(int32_t zeta, uint32_t f0, uint32_t g0, Trans* t) {
-#if ECGPU_DIVSTEPS_MAD
         uint64_t u = 1, v = 0, q = 0, r = 1, f = f0, g = g0;           // the values are the LOWER halves
 #pragma unroll 5
         for (int i = 0; i < 30; i++) {
@@ -143,32 +138,6 @@ struct ModInv {
         t->q = (int32_t)(uint32_t)q;
         t->r = (int32_t)(uint32_t)r;
         return zeta;
-#else
-        uint32_t u = 1, v = 0, q = 0, r = 1;
-        uint32_t f = f0, g = g0;
-#pragma unroll 5
-        for (int i = 0; i < 30; i++) {
-            uint32_t c1 = (uint32_t)(zeta >> 31);          // all ones iff zeta < 0  (delta > 0)
-            uint32_t c2 = 0u - (g & 1u);                   // all ones iff g odd
-            uint32_t x = (f ^ c1) - c1, y = (u ^ c1) - c1, z = (v ^ c1) - c1;   // conditionally negated f, u, v
-            g += x & c2;
-            q += y & c2;
-            r += z & c2;
-            c1 &= c2;                                      // swap iff delta > 0 and g odd
-            zeta = (int32_t)((uint32_t)zeta ^ c1) - 1;
-            f += g & c1;
-            u += q & c1;
-            v += r & c1;
-            g >>= 1;
-            u <<= 1;
-            v <<= 1;
-        }
-        t->u = (int32_t)u;
-        t->v = (int32_t)v;
-        t->q = (int32_t)q;
-        t->r = (int32_t)r;
-        return zeta;
-#endif
     }
 
     // acc + a b on signed 32-bit factors.  On the device as v_mad_i64_i32 by hand: the limbs are known to be non-negative, the

@@ -24,9 +24,9 @@
 //   finish      one lane per (window, bucket): adds the bucket's 1-2 partial sums; a bucket with more than 32 of them
 //               (degenerate inputs) is handed to a whole workgroup
 //   reduce      running-sum trick on segments of buckets, segment sums, window sums (LDS trees; k256: additions on quad lanes)
-//   combine     Horner over the windows (c doublings each) on ONE wave: k256 complete doublings / additions on quad lanes in
-//               homogeneous coordinates (msm_hom_dbl_quad / msm_hom_add_quad), the a = -3 sets Jacobian doublings on three
-//               lanes; the result leaves as an affine wire record
+//   combine     Horner over the windows (c doublings each) on ONE wave: k256 complete doublings on the rows of the wave
+//               (ecgpu_rows.h) and complete additions on quad lanes (msm_hom_add_quad), both in homogeneous coordinates; the
+//               a = -3 sets Jacobian doublings on three lanes; the result leaves as an affine wire record
 //
 // Workspace layout (one allocation, offsets in MsmPlan): packed affine points [n][2N] u32,
 // digits [nwin][n] u16 + validity bits [nwin][n/64] u64, tile histograms [nwin][ntiles][NB] u32 (one-level sort) / the level-A
@@ -44,11 +44,6 @@
 #include "ecgpu_knobs.h"
 #include "ecgpu_msm_chunk.h"
 #include "ecgpu_rows.h"
-
-// -DECGPU_MSM_COMBINE_ROWS=0: the doublings of the k256 Horner chain on quad lanes as in round 4 (A/B: profiles/r05/msm_combine_rows_ab.txt)
-#ifndef ECGPU_MSM_COMBINE_ROWS
-#define ECGPU_MSM_COMBINE_ROWS 1
-#endif
 
 namespace ecgpu {
 
@@ -704,16 +699,14 @@ struct MsmPartialsHbm {       // [slot][4] raw elements: X, Y, ZZ, ZZZ
 };
 
 // one lane per (window, chunk)
-// (-DECGPU_MSM_ACC_WAVES=4, an A/B knob of the build: 128 registers + 108 bytes of scratch per lane for k256 — measured 10 % slower,
-// 15.8 against 14.4 ms at 2^24 terms, profiles/r04/msm_accumulate_four_waves_ab.txt)
-#ifndef ECGPU_MSM_ACC_WAVES
-#define ECGPU_MSM_ACC_WAVES 3
-#endif
-static_assert(ECGPU_MSM_ACC_WAVES >= 1 && ECGPU_MSM_ACC_WAVES <= 4,
+// Three waves per SIMD for the sets up to 256 bits.  Four (128 registers + 108 bytes of scratch per lane for k256) measured 10 %
+// slower, 15.8 against 14.4 ms at 2^24 terms: profiles/r04/msm_accumulate_four_waves_ab.txt, DESIGN section 8.
+constexpr int MSM_ACC_WAVES = 3;
+static_assert(MSM_ACC_WAVES >= 1 && MSM_ACC_WAVES <= 4,
               "the k256 reduction's assembly blocks own v[94:127] (ecgpu_k256_reduce_asm.h): a kernel that includes them needs 128 VGPRs, "
               "i.e. at most four waves per SIMD");
 template <class C>
-__global__ void __launch_bounds__(64, C::N <= 8 ? ECGPU_MSM_ACC_WAVES : C::N <= 12 ? 2 : 1)
+__global__ void __launch_bounds__(64, C::N <= 8 ? MSM_ACC_WAVES : C::N <= 12 ? 2 : 1)
 k_msm_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ sorted,
                  const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, size_t n, size_t nb,
                  int nwin, size_t chunk, size_t nchunks, uint32_t* __restrict__ partials, uint32_t* __restrict__ zero_word) {
@@ -729,25 +722,9 @@ k_msm_accumulate(const uint32_t* __restrict__ pts, const uint32_t* __restrict__ 
     msm_chunk_accumulate<C>(sorted + w * n, ow, total, (uint32_t)nb, (uint32_t)chunk, (uint32_t)q, G::curve_b(), points, sink);
 }
 
-// -DECGPU_MSM_FUSED_TAIL=0: bucket finish and running sums as the two launches of round 4 (A/B: profiles/r05/)
-#ifndef ECGPU_MSM_FUSED_TAIL
-#define ECGPU_MSM_FUSED_TAIL 1
-#endif
-// The fused tail kernel (k_msm_finish_segments: the bucket finish inside the running sums — no launch and no round trip of the
-// bucket sums) is built and correct but NOT the default: measured on MI355X (profiles/r05/msm_tail_fused_ab.txt), k256, before
-// the reduction went to assembly: 0.365 against 0.391 ms at 2^24 terms, 0.32 against 0.27 at 2^21 GLV terms (65,536 segment lanes
-// = one wave per SIMD, every lane a chain of 4 x ~3 stretches + 29 point operations; a lane per BUCKET is four times the
-// parallelism for the stretch sums).  With the assembly reduction k_msm_bucket_finish needs 168 registers instead of 256 + scratch
-// and runs three waves per SIMD: the two launches then win at both sizes (0.49 against 0.64 ms at 2^24, 0.37 against 0.40 at 2^21
-// on a box with slow tail kernels).  ECGPU_MSM_FUSED_TAIL=1 selects the fused form (sets up to 384 bits: the twenty-limb p521 does
-// not fit its registers).
-template <class C>
-inline bool msm_fused_tail(const MsmPlan& p) {
-    (void)p;
-    if (const char* e = knob("ECGPU_MSM_FUSED_TAIL")) return e[0] == '1' && ECGPU_MSM_FUSED_TAIL != 0 && C::N <= 12;
-    return false;
-}
-
+// The tail is two launches, k_msm_bucket_finish and k_msm_reduce_segments.  One fused kernel (the bucket finish inside the running
+// sums: a lane per SEGMENT, a quarter of the parallelism for the stretch sums) lost at both sizes once the k256 reduction went to
+// assembly, 0.64 against 0.49 ms at 2^24 terms and 0.40 against 0.37 at 2^21: profiles/r05/msm_tail_fused_ab.txt.
 // A bucket normally has one or two partial sums.  A degenerate input (all scalars equal, all ones) gives ONE bucket
 // per window thousands of them; such buckets are handed to a whole workgroup each (k_msm_big_buckets) instead of
 // being walked by a single lane.
@@ -816,31 +793,12 @@ k_msm_big_buckets(const uint32_t* __restrict__ partials, const uint32_t* __restr
 }
 constexpr unsigned MSM_BIG_GRID = 256;
 
-// the buckets k_msm_big_buckets takes, listed BEFORE the accumulation (counts and offsets are all it needs): one lane per
-// (window, bucket).  For the fused tail below, which has no per-bucket launch of its own to do the listing in.
-static __global__ void __launch_bounds__(256)
-k_msm_find_big(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ offsets, size_t nbk, uint32_t chunk,
-               uint32_t* __restrict__ big_list, uint32_t max_big) {
-    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= nbk) return;
-    const uint32_t first = offsets[gid], cnt = counts[gid];
-    if (cnt != 0 && (first + cnt - 1) / chunk - first / chunk >= MSM_BIG_PARTIALS) {
-        const uint32_t slot = atomicAdd(big_list, 1u);
-        if (slot < max_big) big_list[1 + slot] = (uint32_t)gid;     // (always: max_big is an upper bound)
-    }
-}
-
-// ---- a = 0 (k256): one COMPLETE projective doubling spread over the four lanes of a quad -----------------------------------
-// Renes–Costello–Batina's doubling for a = 0 (the formulas of Group::dbl_a0: X3 = 2 XY (Y^2 - 9b Z^2), Y3 = 24b Y^2 Z^2 +
-// (Y^2 - 9b Z^2)(Y^2 + 3b Z^2), Z3 = 8 Y^3 Z) has only TWO dependent levels of products, four products each:
-//      {Y^2, Y Z, Z^2, X Y}   ->   {3b Z^2 * 8 Y^2,  Y Z * 8 Y^2,  (Y^2 - 9b Z^2)(Y^2 + 3b Z^2),  (Y^2 - 9b Z^2) * 2 X Y}
-// against three for the Jacobian doubling above, and the accumulator never leaves the homogeneous form the additions of the
-// Horner chain want (no conversion to Jacobian coordinates and back around every run of doublings, no special case for the
-// identity).  Lane r of every quad computes product r of a level; a quad hands its four results round with DPP quad
-// permutes — plain vector moves, no LDS round trip — and the three multiplications by small constants between the levels are one
-// more per-lane step.  ~550 instructions per doubling on the critical path instead of ~800.
-// Every lane must enter with the same point; Y is carried with limb magnitude 2 (the sum that ends a doubling is not
-// normalised: the products of the next one have the room).
+// ---- a = 0 (k256): complete projective additions spread over the four lanes of a quad ----------------------------------------
+// Lane r of every quad computes product r of a level of dependent products; a quad hands its results round with DPP quad
+// permutes (msm_quad_bcast<K>: lane K of every quad to its four lanes) — plain vector moves, no LDS round trip — and the
+// multiplications by small constants between the levels are one more per-lane step.  Every lane must enter with the same point.
+// (The doublings of the Horner chain were spread over quads the same way, 569 instructions each; on the rows of the wave,
+// ecgpu_rows.h, they are ~190: profiles/r05/msm_combine_rows_ab.txt, profiles/r05/isa_loops.txt.)
 template <int K, class M>
 __device__ __forceinline__ M msm_quad_bcast(const M& v) {
     M r;
@@ -849,30 +807,7 @@ __device__ __forceinline__ M msm_quad_bcast(const M& v) {
         r.e.v[i] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v.e.v[i], K * 0x55, 0xf, 0xf, false);
     return r;
 }
-template <class C>
-__device__ __forceinline__ void msm_hom_dbl_quad(typename Field<C>::M1& X, Mag<C, 2, 2>& Y, typename Field<C>::M1& Z, int role) {
-    using F = Field<C>;
-    static_assert(C::A_IS_ZERO && C::REPR == REPR_U29_K256, "a = 0 on the 9 x 29 field");
-    constexpr uint32_t b3 = 3 * C::B_SMALL;
-    static_assert(3 * b3 < (1u << 12), "small-constant multiplier");
-    // level 1:  Y^2 | Y Z | Z^2 | X Y
-    const auto p1 = F::mul(F::sel(role == 2, Z, F::sel(role == 3, X, Y)), F::sel(role == 0 || role == 3, Y, Z));   // 2*2 = 4
-    const auto yy = msm_quad_bcast<0>(p1), yz = msm_quad_bcast<1>(p1), zz = msm_quad_bcast<2>(p1), xy = msm_quad_bcast<3>(p1);
-    // small constants:  3b Z^2 | 9b Z^2 | 8 Y^2 | (unused)
-    const auto ps = F::template wrap<1, 1>(F::k_mul_small(F::sel(role < 2, zz, yy).e, role == 0 ? b3 : role == 1 ? 3 * b3 : 8u));
-    const auto bzz3 = msm_quad_bcast<0>(ps), bzz9 = msm_quad_bcast<1>(ps), yy8 = msm_quad_bcast<2>(ps);
-    const auto yy_m9 = F::sub(yy, bzz9);                           // 3
-    const auto yy_p3 = F::add(yy, bzz3);                           // 2
-    const auto xy2 = F::dbl(xy);                                   // 2
-    // level 2:  3b Z^2 * 8 Y^2 | Y Z * 8 Y^2 | (Y^2 - 9b Z^2)(Y^2 + 3b Z^2) | (Y^2 - 9b Z^2) * 2 X Y
-    const auto p2 = F::mul(F::sel(role == 0, bzz3, F::sel(role == 1, yz, yy_m9)),
-                           F::sel(role < 2, yy8, F::sel(role == 2, yy_p3, xy2)));                                   // 3*2 = 6
-    X = msm_quad_bcast<3>(p2);
-    Z = msm_quad_bcast<1>(p2);
-    Y = F::add(msm_quad_bcast<0>(p2), msm_quad_bcast<2>(p2));
-}
-
-// The complete addition of the chain (Group::add_a0's formulas) the same way: its twelve products are two dependent levels of
+// The complete addition (Group::add_a0's formulas): its twelve products are two dependent levels of
 // three + three (the second with the subtractions of the first folded into its reduction, F::mul_sub) and one level of three
 // two-product sums (F::mul2) — lanes 0..2 of every quad; ~1000 instructions on the critical path instead of ~2150.
 // All coordinates enter and leave with magnitude 1.
@@ -1024,45 +959,6 @@ k_msm_reduce_segments(const uint32_t* __restrict__ buckets, size_t nb, int seg, 
     store_proj<C>(segs, gid, local);
 }
 
-// The same with the bucket finish inside (round 5): the lane of a segment sums the stretches of its `seg` buckets itself — no
-// k_msm_bucket_finish launch (two rounds of two waves per SIMD whose lanes wait for the slowest bucket of the wave: 0.16 ms at
-// 2^21 terms for ~3 additions per lane) and no round trip of the bucket sums through HBM.  One wave per SIMD and the whole
-// register file: nseg * nwin lanes are one wave per SIMD at 2^21 terms and two rounds of one at 2^24.  Buckets with
-// MSM_BIG_PARTIALS stretches or more (degenerate scalar sets) were listed by k_msm_find_big and summed by k_msm_big_buckets
-// before this kernel runs: they are read from `buckets`.
-template <class C>
-__global__ void __launch_bounds__(64, 1)
-k_msm_finish_segments(const uint32_t* __restrict__ partials, const uint32_t* __restrict__ counts,
-                      const uint32_t* __restrict__ offsets, const uint32_t* __restrict__ pts,
-                      const uint32_t* __restrict__ sorted, size_t n, size_t nb, int nwin, size_t chunk, size_t nchunks,
-                      const uint32_t* __restrict__ buckets, int seg, size_t nseg, int top_shift, uint32_t* __restrict__ segs) {
-    using G = Group<C>;
-    size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= nseg * nwin) return;
-    size_t w = gid / nseg, s = gid % nseg;
-    const Fe<C::NL> b = G::curve_b();
-    MsmPartialsHbm<C> src{const_cast<uint32_t*>(partials) + w * (nb + nchunks) * (4 * Field<C>::NS)};
-    MsmPointsHbm<C> points{pts};
-    Proj<C> running = G::identity(), local = G::identity();
-    size_t base = s * seg;
-    const int sh = (int)w == nwin - 1 ? top_shift : 0;
-#pragma unroll 1
-    for (int j = seg - 1; j >= 0; j--) {
-        const size_t gb = w * nb + base + j;
-        const uint32_t first = offsets[gb], cnt = counts[gb];
-        Proj<C> bk;
-        if (cnt != 0 && (first + cnt - 1) / (uint32_t)chunk - first / (uint32_t)chunk >= MSM_BIG_PARTIALS)
-            bk = load_proj<C>(buckets, gb);
-        else
-            bk = msm_bucket_finish<C>((uint32_t)(base + j), first, cnt, (uint32_t)chunk, b, src, sorted + w * n, points);
-        running = G::add(running, bk, b);
-        if (j > 0 && ((base + j) >> sh) != ((base + j - 1) >> sh)) local = G::add(local, running, b);
-    }
-    uint32_t wmin = (uint32_t)(base >> sh) + 1;
-    local = G::add(local, wmin == 1 ? running : small_mul<C>(running, wmin, b), b);
-    store_proj<C>(segs, gid, local);
-}
-
 // parts[w][g] = sum of the segment sums segs[w][g * per .. (g + 1) * per): one workgroup per (g, w), a strided pass
 // and an LDS tree.  With the default plan (4 buckets per segment, 256 segments per workgroup) a lane adds one segment:
 // the depth is the 8 levels of the tree, where one workgroup per window used to walk 32 segments per lane first.
@@ -1098,7 +994,7 @@ k_msm_window_sums(const uint32_t* __restrict__ parts, int nranks, int nwin, int 
     if (threadIdx.x == 0) store_proj<C>(wins, blockIdx.x, acc);
 }
 
-// ---- one Jacobian doubling spread over three lanes of a wave (the a = -3 sets; k256: msm_hom_dbl_quad below) ------------------
+// ---- one Jacobian doubling spread over three lanes of a wave (the a = -3 sets; k256: RowsDblK256, ecgpu_rows.h) ------------------
 // The Horner chain below is ONE dependency chain of c * (nwin - 1) doublings (120 for 128-bit sub-scalars, 240 for 255-bit
 // ones): a single lane issues one instruction every ~5 cycles, so the chain's time is its instruction count.  A doubling's
 // seven or eight field multiplications are only three or four DEPENDENT levels:
@@ -1126,7 +1022,7 @@ __device__ __forceinline__ Jac<C> msm_jac_dbl_lanes(const Jac<C>& p, int lane) {
     using F = Field<C>;
     auto X = G::mj(p.x), Y = G::mj(p.y), Z = G::mj(p.z);
     Jac<C> o;
-    static_assert(!C::A_IS_ZERO, "k256 takes the complete doublings on quad lanes (msm_hom_dbl_quad)");
+    static_assert(!C::A_IS_ZERO, "k256 takes the complete doublings on the rows of the wave (RowsDblK256)");
     {
         const auto p1 = F::sqr(msm_sel3<C>(lane, Z, Y, F::add(Y, Z)));                              // delta | gamma | (Y + Z)^2
         const auto delta = msm_lane_bcast(p1, 0), gamma = msm_lane_bcast(p1, 1), yz = msm_lane_bcast(p1, 2);
@@ -1162,13 +1058,11 @@ __global__ void __launch_bounds__(64) k_msm_combine(const uint32_t* __restrict__
     Fe<C::NL> b = G::curve_b();
     Proj<C> acc = load_proj<C>(vw, nwin - 1);
     if constexpr (C::A_IS_ZERO && C::REPR == REPR_U29_K256) {
-        // complete doublings and additions in the accumulator's own (homogeneous) form, the products of a level on the lanes of
-        // a quad (msm_hom_dbl_quad, msm_hom_add_quad); every quad of the wave computes the same thing
+        // complete doublings and additions in the accumulator's own (homogeneous) form: the c doublings between two windows on the
+        // ROWS of the wave (ecgpu_rows.h: one limb per lane, the four products of a level on the four rows), the addition of a
+        // window's sum with the products of a level on the lanes of a quad (msm_hom_add_quad; every quad computes the same thing)
         const int role = lane & 3;
         auto X = G::m(acc.x), Y = G::m(acc.y), Z = G::m(acc.z);
-#if ECGPU_MSM_COMBINE_ROWS
-        // round 5: the c doublings between two windows on the ROWS of the wave (ecgpu_rows.h: one limb per lane, the four products of
-        // a level on the four rows; ~190 instructions per doubling instead of 569), the addition of a window's sum on quad lanes as before
         __shared__ uint32_t rows_lds[48];
         RowsDblK256 rd;
         rd.init();
@@ -1186,17 +1080,6 @@ __global__ void __launch_bounds__(64) k_msm_combine(const uint32_t* __restrict__
             Z = Field<C>::template wrap<1, 1>(z2);
             msm_hom_add_quad<C>(X, Y, Z, q, role);
         }
-#else
-#pragma unroll 1
-        for (int w = nwin - 2; w >= 0; w--) {
-            const Proj<C> q = load_proj<C>(vw, w);                      // in flight under the doublings
-            auto Yw = Field<C>::template wrap<2, 2>(Y.e);
-#pragma unroll 1
-            for (int s = 0; s < c; s++) msm_hom_dbl_quad<C>(X, Yw, Z, role);
-            Y = Field<C>::norm(Yw);
-            msm_hom_add_quad<C>(X, Y, Z, q, role);
-        }
-#endif
         acc.x = X.e;
         acc.y = Y.e;
         acc.z = Z.e;
@@ -1279,18 +1162,13 @@ inline int msm_window_bits(size_t n, bool glv) {
 // became three times cheaper (rows of a wave, round 5) while the halves still double prepare and sort, and the round-6 sweep with
 // HEAD's kernels (tools/gpu_msm_crossover.py, profiles/r06/msm_glv_crossover_*.txt) reads, best GLV (c = 15) / best plain (c = 16):
 // 1.467 / 1.547 ms at 2^20 terms, 2.528 / 2.468 at 2^21, 5.00 / 4.38 at 2^22 — the lines cross at about 1.6 x 2^20 terms.
-// ECGPU_MSM_GLV = 0 / 1 forces it off / on, ECGPU_MSM_GLV_MAX_LOG2 moves the threshold to a power of two (tuning knobs of the tool
-// build; results do not depend on them).
+// ECGPU_MSM_GLV = 0 / 1 forces it off / on (a tuning knob of the tool build; results do not depend on it).
 template <class C>
 bool msm_use_glv(size_t n) {
     if (!MsmHasGlv<C>::value) return false;
     if (const char* e = knob("ECGPU_MSM_GLV")) {
         if (e[0] == '0') return false;
         if (e[0] == '1') return true;
-    }
-    if (const char* e = knob("ECGPU_MSM_GLV_MAX_LOG2")) {
-        const int max_log2 = atoi(e);
-        return max_log2 >= 0 && max_log2 < 40 && n <= ((size_t)1 << max_log2);
     }
     return n < MSM_GLV_MAX_TERMS;
 }
@@ -1440,26 +1318,15 @@ void launch_msm_tail(const MsmPlan& p, hipStream_t stream, uint8_t* ws, uint32_t
     uint32_t* segs = (uint32_t*)(ws + p.off_segs);
     const size_t nbk = p.nb * p.nwin;
     size_t nsg = p.nseg * p.nwin;
-    if (msm_fused_tail<C>(p)) {
-        // (k_msm_find_big ran before the accumulation: launch_msm_parts)
-        hipLaunchKernelGGL(k_msm_big_buckets<C>, dim3(MSM_BIG_GRID), dim3(BLOCK), 0, stream, (const uint32_t*)partials,
-                           (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts, (const uint32_t*)sorted, ne, p.nb,
-                           p.chunk, p.nchunks, buckets, (const uint32_t*)big_list, (uint32_t)p.max_big);
-        hipLaunchKernelGGL((k_msm_finish_segments<C>), dim3((unsigned)((nsg + 63) / 64)), dim3(64), 0, stream,
-                           (const uint32_t*)partials, (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts,
-                           (const uint32_t*)sorted, ne, p.nb, p.nwin, p.chunk, p.nchunks, (const uint32_t*)buckets, p.seg, p.nseg,
-                           msm_top_shift(p.kbits, p.c), segs);
-    } else {
-        // (big_list[0] = 0 was written by the first lane of k_msm_accumulate)
-        hipLaunchKernelGGL((k_msm_bucket_finish<C>), dim3((unsigned)((nbk + 63) / 64)), dim3(64), 0, stream,
-                           (const uint32_t*)partials, (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts,
-                           (const uint32_t*)sorted, ne, p.nb, p.nwin, p.chunk, p.nchunks, buckets, big_list, (uint32_t)p.max_big);
-        hipLaunchKernelGGL(k_msm_big_buckets<C>, dim3(MSM_BIG_GRID), dim3(BLOCK), 0, stream, (const uint32_t*)partials,
-                           (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts, (const uint32_t*)sorted, ne, p.nb,
-                           p.chunk, p.nchunks, buckets, (const uint32_t*)big_list, (uint32_t)p.max_big);
-        hipLaunchKernelGGL((k_msm_reduce_segments<C>), dim3((unsigned)((nsg + 63) / 64)), dim3(64), 0, stream,
-                           (const uint32_t*)buckets, p.nb, p.seg, p.nseg, p.nwin, msm_top_shift(p.kbits, p.c), segs);
-    }
+    // (big_list[0] = 0 was written by the first lane of k_msm_accumulate)
+    hipLaunchKernelGGL((k_msm_bucket_finish<C>), dim3((unsigned)((nbk + 63) / 64)), dim3(64), 0, stream,
+                       (const uint32_t*)partials, (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts,
+                       (const uint32_t*)sorted, ne, p.nb, p.nwin, p.chunk, p.nchunks, buckets, big_list, (uint32_t)p.max_big);
+    hipLaunchKernelGGL(k_msm_big_buckets<C>, dim3(MSM_BIG_GRID), dim3(BLOCK), 0, stream, (const uint32_t*)partials,
+                       (const uint32_t*)counts, (const uint32_t*)offsets, (const uint32_t*)pts, (const uint32_t*)sorted, ne, p.nb,
+                       p.chunk, p.nchunks, buckets, (const uint32_t*)big_list, (uint32_t)p.max_big);
+    hipLaunchKernelGGL((k_msm_reduce_segments<C>), dim3((unsigned)((nsg + 63) / 64)), dim3(64), 0, stream,
+                       (const uint32_t*)buckets, p.nb, p.seg, p.nseg, p.nwin, msm_top_shift(p.kbits, p.c), segs);
     if (p.detail[1]) (void)hipEventRecord(p.detail[1], stream);
     hipLaunchKernelGGL((k_msm_reduce_windows<C>), dim3((unsigned)p.nparts, (unsigned)p.nwin), dim3(BLOCK), 0, stream,
                        (const uint32_t*)segs, p.nseg, p.per_part, parts);
@@ -1536,11 +1403,7 @@ void launch_msm_parts(const MsmPlan& p, hipStream_t stream, const uint8_t* d_sca
         hipLaunchKernelGGL(k_msm_sort_a, dim3((unsigned)p.ntiles2, (unsigned)p.nwin), dim3(1024), 0, stream, (const uint16_t*)digits,
                            (const unsigned long long*)vmask, ne, p.sort_bits_b, p.idx_bits, (uint32_t)p.npart, cursor, tmp);
         // level B: one workgroup per (partition, window); small partitions (small MSMs) get 256 lanes
-        unsigned tb = ne / p.npart >= 4096 ? 1024u : 256u;
-        if (const char* e = knob("ECGPU_MSM_SORTB_T")) {            // tuning knob: lanes per level-B workgroup
-            const int v = atoi(e);
-            if (v == 256 || v == 512 || v == 1024) tb = (unsigned)v;
-        }
+        const unsigned tb = ne / p.npart >= 4096 ? 1024u : 256u;
         hipLaunchKernelGGL(k_msm_sort_b, dim3((unsigned)p.npart, (unsigned)p.nwin), dim3(tb), 0, stream, (const uint32_t*)tmp, ne,
                            p.sort_bits_b, p.idx_bits, (uint32_t)p.npart, big, (const uint32_t*)offsets_a, (const uint32_t*)counts_a,
                            counts, offsets, sorted);
@@ -1589,19 +1452,12 @@ void launch_msm_parts(const MsmPlan& p, hipStream_t stream, const uint8_t* d_sca
                            (const uint16_t*)digits, (const unsigned long long*)vmask, ne, p.tile, p.nb,
                            (const uint32_t*)tile_hist, (const uint32_t*)offsets, sorted);
     }
-    if (msm_fused_tail<C>(p)) {                         // the buckets k_msm_big_buckets will take, listed while nothing waits for it
-        uint32_t* big_list = (uint32_t*)(ws + p.off_biglist);
-        const size_t nbk = p.nb * p.nwin;
-        (void)hipMemsetAsync(big_list, 0, 4, stream);
-        hipLaunchKernelGGL(k_msm_find_big, dim3((unsigned)((nbk + 255) / 256)), dim3(256), 0, stream, (const uint32_t*)counts,
-                           (const uint32_t*)offsets, nbk, (uint32_t)p.chunk, big_list, (uint32_t)p.max_big);
-    }
     if (ev_sorted) (void)hipEventRecord(ev_sorted, stream);
     size_t nlanes = p.nchunks * p.nwin;
     hipLaunchKernelGGL(k_msm_accumulate<C>, dim3((unsigned)((nlanes + 63) / 64)), dim3(64), 0, stream,
                        (const uint32_t*)pts, (const uint32_t*)sorted, (const uint32_t*)counts,
                        (const uint32_t*)offsets, ne, p.nb, p.nwin, p.chunk, p.nchunks, partials,
-                       msm_fused_tail<C>(p) ? (uint32_t*)nullptr : (uint32_t*)(ws + p.off_biglist));
+                       (uint32_t*)(ws + p.off_biglist));
     if (ev_accumulated) (void)hipEventRecord(ev_accumulated, stream);       // the accumulation kernel alone (round 4 recorded this after the bucket finish)
     launch_msm_tail<C>(p, stream, ws, parts);
 }

@@ -55,10 +55,6 @@ struct Xyzz {
     Fe<C::NL> x, y, zz, zzz;
 };
 
-template <class C, int L, int V>
-std::integral_constant<int, V> magv(const Mag<C, L, V>&);
-
-
 template <class C>
 struct Group {
     using F = Field<C>;

@@ -328,16 +328,6 @@ struct K256Scalar {
         reduce_wide(r, l);
     }
 
-    // round(a*b / 2^384)                            wide64.rs:64-119 with shift = 384
-    static ECGPU_HD void mul_shift_384(uint32_t* r, const uint32_t* a, const uint32_t* b) {
-        uint32_t l[16];
-        mp_mul<8>(l, a, b);
-        uint32_t res[8] = {l[12], l[13], l[14], l[15], 0, 0, 0, 0};
-        uint32_t round_bit = l[11] >> 31;
-        uint32_t one[8] = {round_bit, 0, 0, 0, 0, 0, 0, 0};
-        add(r, res, one);
-    }
-
     // ---- the GLV split on 29-bit limbs -----------------------------------------------------------------------------------------
     // k -> (r1, r2) with r1 + r2 lambda = k (mod n)    mul/glv.rs:149-156
     // The reference computes c1 = round(k g1 / 2^384) (-b1), c2 = round(k g2 / 2^384) (-b2), r2 = c1 + c2, r1 = k - r2 lambda,

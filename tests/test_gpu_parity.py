@@ -26,7 +26,7 @@ def eng():
 def keng():
     """An engine on the TOOL build of the library (lib/libecgpu_knobs.so, csrc/ecgpu_knobs.h): the same kernel objects, but the ECGPU_*
     tuning knobs are read from the environment — the product library never reads it.  The tests that force a code path the planner
-    would not pick at their sizes (two-level sort at small n, chunk sizes, the chunked host-pointer MSM, the fused tail) run on it."""
+    would not pick at their sizes (two-level sort at small n, chunk sizes, the chunked host-pointer MSM) run on it."""
     ecgpu = ecgpu_module()
     e = ecgpu.Engine(0, variant="knobs")
     yield e
@@ -1661,11 +1661,10 @@ def test_generator_table_policy_budget_and_pinning():
 
 
 @pytest.mark.parametrize("curve", ["k256", "p256", "p384"])
-def test_msm_fused_tail_form(eng, keng, curve, monkeypatch):
-    """ECGPU_MSM_FUSED_TAIL=1: the bucket finish inside the running sums (k_msm_finish_segments, with the degenerate buckets listed
-    by k_msm_find_big before the accumulation and summed by k_msm_big_buckets) — not the default form, kept
-    correct: random scalars, and a scalar set that puts thousands of terms into single buckets, against the default form and the
-    exact dot product."""
+def test_msm_few_distinct_scalars(eng, curve):
+    """The bucket method against the exact dot product (sum k_i s_i mod n) G: random scalars, and a set of three distinct scalars,
+    which gives every window three buckets with thousands of terms — far past MSM_BIG_PARTIALS partial sums each, so that
+    k_msm_bucket_finish hands them to k_msm_big_buckets."""
     c = pyec.CURVES[curve]
     n = (1 << 18) + 333                                   # (above every curve's small-MSM threshold: the bucket method)
     s = rand_scalars(c.cid, n, 0xEC0061F7 + c.cid)
@@ -1674,11 +1673,7 @@ def test_msm_fused_tail_form(eng, keng, curve, monkeypatch):
         k = rand_scalars(c.cid, n, 0xEC0062F7 + c.cid)
         if case != "random":
             k = np.tile(k[: 3 * c.L], n // 3 + 1)[: n * c.L].copy()          # three scalars: every window has three huge buckets
-        want, wf = eng.lincomb(c.cid, k, pts)
-        monkeypatch.setenv("ECGPU_MSM_FUSED_TAIL", "1")
-        got, gf = keng.lincomb(c.cid, k, pts)
-        monkeypatch.delenv("ECGPU_MSM_FUSED_TAIL")
-        assert bytes(got) == bytes(want) and gf == wf, (curve, case)
+        got, gf = eng.lincomb(c.cid, k, pts)
         ki = [int.from_bytes(bytes(k[i * c.L:(i + 1) * c.L]), "big") for i in range(n)]
         si = [int.from_bytes(bytes(s[i * c.L:(i + 1) * c.L]), "big") for i in range(n)]
         dot = sum(a * b for a, b in zip(ki, si)) % c.n

@@ -2,8 +2,7 @@
 # A second build of libecgpu.so for A/B measurements (the `ab:` recipe of tools/gpu_run.sh loads it through ECGPU_TOOL_LIB): the named
 # translation units are recompiled with extra flags into elliptic-curves_amd/build_alt/, everything else is linked from the main
 # build.      bash tools/build_alt_lib.sh <suffix> "<extra hipcc flags>" <group>_<Curve> [...]
-#   bash tools/build_alt_lib.sh nofused "-DECGPU_FUSED_SUB=0" var_P256Params var_P384Params        -> lib/libecgpu_nofused.so
-#   bash tools/build_alt_lib.sh acc4 "-DECGPU_MSM_ACC_WAVES=4" msm_K256Params                      -> lib/libecgpu_acc4.so
+#   bash tools/build_alt_lib.sh cred "-DECGPU_K256_ASM_REDUCE=0" var_K256Params msm_K256Params     -> lib/libecgpu_cred.so
 # (the alternative libraries are build artefacts: git-ignored, they travel to the GPU box with the snapshot)
 set -eu
 cd "$(dirname "$0")/../elliptic-curves_amd"

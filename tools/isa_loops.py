@@ -5,7 +5,7 @@ the inversion in k_normalize).  Compiles the kernel group's translation unit wit
 
     python tools/isa_loops.py <group> <CurveParams> <mangled-name substring> [extra hipcc flags ...]
     python tools/isa_loops.py msm K256Params k_msm_combine
-    python tools/isa_loops.py msm K256Params k_msm_combine -DECGPU_MSM_COMBINE_ROWS=0
+    python tools/isa_loops.py msm K256Params k_msm_accumulate -DECGPU_K256_ASM_REDUCE=0
     python tools/isa_loops.py base K256Params k_normalizeINS_10K256ParamsELi0E
 """
 import collections
