@@ -757,6 +757,10 @@ class Engine:
         self._chk(fn(self._ctx, curve, _dp(d_scalars), _dp(d_points_xy), _dp(d_points_inf), ctypes.c_size_t(n), _dp(d_out_xy),
                      _dp(d_out_inf)))
 
+    def mul_by_generator_and_mul_add_dev(self, curve, d_a, d_b, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf=None):
+        self._chk(self._lib.ecgpu_batch_mul_base_and_mul_add_dev(self._ctx, curve, _dp(d_a), _dp(d_b), _dp(d_points_xy), _dp(d_points_inf),
+                                                                 ctypes.c_size_t(n), _dp(d_out_xy), _dp(d_out_inf)))
+
     def lincomb_dev(self, curve, d_scalars, d_points_xy, d_points_inf, n, d_out_xy, d_out_inf):
         self._chk(self._lib.ecgpu_msm_dev(self._ctx, curve, _dp(d_scalars), _dp(d_points_xy), _dp(d_points_inf),
                                           ctypes.c_size_t(n), _dp(d_out_xy), _dp(d_out_inf)))
