@@ -600,7 +600,7 @@ int normalize_out(ecgpu_ctx* ctx, size_t n, void* d_out_xy, void* d_out_inf, boo
 // The one call frame of the device-pointer pipelines (the counterpart of HostCall / staged below).  An implementation states
 //   what it does for an empty call, before the frame: a call that uses the comb table or the generator LUTs builds them for
 //       n == 0 too (ensure_table / ensure_ct_lut come first), a reducing call writes the identity, every other returns at once;
-//   what it reserves: {buffer, bytes[, wanted]} in order — grown before anything is queued;
+//   what it reserves: {buffer, bytes[, wanted]} in order (a shared pipeline's list, then its caller's) — grown before anything is queued;
 //   its wipe set: WIPE_* flags (0 for the variable-time forms), zeroed behind the call's last kernel on EVERY path out, early error
 //       returns included (CtWipe);
 //   its launches between marks: the constructor has joined the MSM lanes and cleared the status word (reset_status) before the
@@ -612,9 +612,11 @@ struct DevCall {
     ecgpu_ctx* ctx;
     CtWipe wipe;
     int rc = ECGPU_OK;         // not ECGPU_OK after the constructor: nothing was queued, the implementation returns it
-    DevCall(ecgpu_ctx* c, int wipe_set, std::initializer_list<Reserve> bufs) : ctx(c), wipe(c, wipe_set) {
-        for (const Reserve& r : bufs)
-            if (r.wanted && (rc = ensure(ctx, r.buf, r.bytes)) != ECGPU_OK) return;
+    DevCall(ecgpu_ctx* c, int wipe_set, std::initializer_list<Reserve> bufs, std::initializer_list<Reserve> more = {})
+        : ctx(c), wipe(c, wipe_set) {
+        for (const auto& list : {bufs, more})
+            for (const Reserve& r : list)
+                if (r.wanted && (rc = ensure(ctx, r.buf, r.bytes)) != ECGPU_OK) return;
         rc = reset_status(ctx);
     }
     void mark(int i) { record(ctx, i); }
@@ -721,6 +723,34 @@ int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void*
     launch_ecdsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)ctx->sg_k.p, (const uint8_t*)ctx->sg_flag.p,
                                 (const uint8_t*)d_z, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, n, normalize_s,
                                 (uint8_t*)d_sig, (uint8_t*)d_recid, (uint8_t*)d_ok);
+    call.mark(2);
+    return call.done();
+}
+
+// BIP340 signing (k256): the fixed-base kernel runs twice, for the key's P = d G and for R = k G
+int schnorr_sign_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_t msg_len, const void* d_aux_rand, size_t n, void* d_out_sig,
+                     void* d_ok) {
+    using C = K256Params;
+    constexpr int NS = Field<C>::NS;
+    int rc;
+    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
+                  {ctx->sg_dp, n * 64 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *dp = (uint8_t*)ctx->sg_dp.p;
+    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
+    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
+    call.mark(0);
+    launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_sk, n, k, flag);                   // d, or 1 in place of an unusable key
+    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // P = d G
+    launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n, dp, k, flag);
+    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    call.mark(1);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
+    launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
     call.mark(2);
     return call.done();
 }
@@ -1471,75 +1501,133 @@ int h2c_run(ecgpu_ctx* ctx, const char* fn, int curve, int mode, const void* d_i
 // ================================================================================================================
 
 namespace {
-// shared driver of the two verification shapes: prepare -> a*G + b*Q -> normalise -> compare
-enum { VERIFY_ECDSA = 0, VERIFY_SCHNORR = 1, VERIFY_SCHNORR_RAW = 2, VERIFY_SM2DSA = 3, VERIFY_RECOVER = 4, VERIFY_BIGN = 5 };
-// mode VERIFY_BIGN: d_h = 32-byte hashes, d_s = 48-byte signatures S0 || S1, d_r unused
-// mode VERIFY_SCHNORR_RAW: d_h = messages (msg_len bytes each), d_s = 64-byte signatures, d_q_xy = 32-byte x-only keys
-// mode VERIFY_RECOVER (public-key recovery): d_q_xy = the recovery id bytes, d_out_xy receives the keys
-template <class C>
-int verify_dev(ecgpu_ctx* ctx, int mode, const void* d_h, const void* d_r, const void* d_s, const void* d_q_xy, size_t n,
-               int reject_high_s, void* d_ok, size_t msg_len = 0, void* d_out_xy = nullptr) {
-    const bool schnorr = mode == VERIFY_SCHNORR || mode == VERIFY_SCHNORR_RAW;
+// ---- signature verification and public-key recovery ------------------------------------------------------------------------
+// The one pipeline of the six schemes: prepare -> u1 G + u2 Q -> normalise -> finish.  A scheme (below) states its own scratch beside
+// the common one, where the normalisation writes (d_xy: read after the reservations, ctx->ec_xy may have grown), and its two stages;
+// both are handed the shared scratch by name.
+struct VerifyScratch {
+    uint8_t *u1, *u2, *q, *valid;      // prepare writes: the scalars of G and of Q, Q as x || y, the verdict so far
+    uint8_t* xy;                       // finish reads: u1 G + u2 Q as x || y records (*d_xy) ...
+    const uint8_t* inf;                // ... and their identity flags
+};
+template <class C, class Prepare, class Finish>
+int verify_pipeline(ecgpu_ctx* ctx, size_t n, std::initializer_list<Reserve> extra, void* const* d_xy, Prepare&& prepare,
+                    Finish&& finish) {
     constexpr int NS = Field<C>::NS;
     const size_t L = 4 * C::N;
     int rc;
     if ((rc = ensure_table<C>(ctx, n)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
     const size_t tstride = var_base_slots<C>(n);
-    // ECDSA verification and recovery invert one scalar per signature: done for the whole batch by Montgomery's trick
-    const bool batch_inv = mode == VERIFY_RECOVER || mode == VERIFY_ECDSA;
-    static_assert(Field<C>::NS >= C::N, "the normalisation's prefix array holds the inverses' prefix products too");
     DevCall call(ctx, 0,
                  {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}, {ctx->ec_u1, n * L}, {ctx->ec_u2, n * L},
-                  {ctx->ec_q, n * 2 * L}, {ctx->ec_valid, n + 16}, {ctx->ec_xy, n * 2 * L, mode != VERIFY_RECOVER}, {ctx->ec_inf, n + 16},
-                  {ctx->ec_r, n * L, mode == VERIFY_SCHNORR_RAW}, {ctx->ec_winv, n * L + 16, batch_inv},
-                  {ctx->prefix, n * Field<C>::NS * 4, batch_inv}});      // (the size normalize_out asks for later)
+                  {ctx->ec_q, n * 2 * L}, {ctx->ec_valid, n + 16}, {ctx->ec_inf, n + 16}}, extra);
     if (call.rc != ECGPU_OK) return call.rc;
-    uint32_t* inv_prefix = batch_inv ? (uint32_t*)ctx->prefix.p : nullptr;
-    uint8_t* inv_out = batch_inv ? (uint8_t*)ctx->ec_winv.p : nullptr;
     const Table& t = ctx->table[C::ID];
     uint32_t* pa = (uint32_t*)ctx->proj.p;
-    uint8_t *u1 = (uint8_t*)ctx->ec_u1.p, *u2 = (uint8_t*)ctx->ec_u2.p, *q = (uint8_t*)ctx->ec_q.p;
-    uint8_t* valid = (uint8_t*)ctx->ec_valid.p;
+    const VerifyScratch v{(uint8_t*)ctx->ec_u1.p, (uint8_t*)ctx->ec_u2.p, (uint8_t*)ctx->ec_q.p, (uint8_t*)ctx->ec_valid.p,
+                          (uint8_t*)*d_xy, (const uint8_t*)ctx->ec_inf.p};
     call.mark(0);
-    if (mode == VERIFY_SCHNORR_RAW) {
-        launch_schnorr_prepare_raw(ctx->stream, (const uint8_t*)d_q_xy, (const uint8_t*)d_h, msg_len, (const uint8_t*)d_s, n, u1,
-                                   u2, q, (uint8_t*)ctx->ec_r.p, valid);
-        d_r = ctx->ec_r.p;
-    } else if (mode == VERIFY_RECOVER)
-        launch_ecdsa_recover_prepare<C>(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_r, (const uint8_t*)d_s,
-                                        (const uint8_t*)d_q_xy, n, reject_high_s, u1, u2, q, valid, inv_prefix, inv_out);
-    else if (mode == VERIFY_SM2DSA)
-        launch_sm2dsa_prepare<C>(ctx->stream, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_q_xy, n, u1, u2, q, valid);
-    else if (mode == VERIFY_BIGN)
-        launch_bign_prepare(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_s, (const uint8_t*)d_q_xy, n, u1, u2, q, valid);
-    else if (schnorr)
-        launch_schnorr_prepare<C>(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_r, (const uint8_t*)d_s,
-                                  (const uint8_t*)d_q_xy, n, u1, u2, q, valid);
-    else
-        launch_ecdsa_prepare<C>(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_r, (const uint8_t*)d_s,
-                                (const uint8_t*)d_q_xy, n, reject_high_s, u1, u2, q, valid, inv_prefix, inv_out);
+    prepare(v);
     call.mark(3);
-    launch_fixed_base<C>(ctx->stream, u1, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
-    launch_var_base<C>(ctx->stream, u2, q, nullptr, n, (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);   // pa[i] += u2[i] Q[i]
+    launch_fixed_base<C>(ctx->stream, v.u1, n, (const uint32_t*)t.d, t.w, t.nwin, pa, ctx->d_status);
+    launch_var_base<C>(ctx->stream, v.u2, v.q, nullptr, n, (uint32_t*)ctx->vtab.p, tstride, nullptr, ctx->d_status, pa);   // pa[i] += u2[i] Q[i]
     call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, mode == VERIFY_RECOVER ? d_out_xy : ctx->ec_xy.p, ctx->ec_inf.p)) != ECGPU_OK) return rc;
-    if (mode == VERIFY_RECOVER)
-        launch_ecdsa_recover_finish<C>(ctx->stream, (uint8_t*)d_out_xy, (const uint8_t*)ctx->ec_inf.p, valid, n, (uint8_t*)d_ok);
-    else if (mode == VERIFY_SM2DSA)
-        launch_sm2dsa_finish<C>(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p,
-                                (const uint8_t*)d_r, valid, n, (uint8_t*)d_ok);
-    else if (mode == VERIFY_BIGN)
-        launch_bign_finish(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p,
-                           (const uint8_t*)d_s, valid, n, (uint8_t*)d_ok);
-    else if (schnorr)
-        launch_schnorr_finish<C>(ctx->stream, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, (const uint8_t*)d_r,
-                                 valid, n, (uint8_t*)d_ok);
-    else
-        launch_ecdsa_finish<C>(ctx->stream, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, (const uint8_t*)d_r,
-                               valid, n, (uint8_t*)d_ok);
+    if ((rc = normalize_out<C>(ctx, n, v.xy, ctx->ec_inf.p)) != ECGPU_OK) return rc;
+    finish(v);
     call.mark(2);
     return call.done(SPANS_VERIFY);
+}
+
+// ECDSA verification and recovery invert one scalar per signature: done for the whole batch by Montgomery's trick, the inverses in
+// ec_winv, their prefix products in ctx->prefix (the size normalize_out asks for later)
+template <class C>
+int ecdsa_verify_dev(ecgpu_ctx* ctx, const void* d_z, const void* d_r, const void* d_s, const void* d_q_xy, size_t n, int reject_high_s,
+                     void* d_ok) {
+    static_assert(Field<C>::NS >= C::N, "the normalisation's prefix array holds the inverses' prefix products too");
+    const size_t L = 4 * C::N;
+    return verify_pipeline<C>(
+        ctx, n, {{ctx->ec_xy, n * 2 * L}, {ctx->ec_winv, n * L + 16}, {ctx->prefix, n * Field<C>::NS * 4}}, &ctx->ec_xy.p,
+        [&](const VerifyScratch& v) {
+            launch_ecdsa_prepare<C>(ctx->stream, (const uint8_t*)d_z, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_q_xy, n,
+                                    reject_high_s, v.u1, v.u2, v.q, v.valid, (uint32_t*)ctx->prefix.p, (uint8_t*)ctx->ec_winv.p);
+        },
+        [&](const VerifyScratch& v) { launch_ecdsa_finish<C>(ctx->stream, v.xy, v.inf, (const uint8_t*)d_r, v.valid, n, (uint8_t*)d_ok); });
+}
+
+// (the keys are normalised straight into the caller's d_out_xy, which the finish kernel then fixes up in place: no ec_xy)
+template <class C>
+int ecdsa_recover_dev(ecgpu_ctx* ctx, const void* d_z, const void* d_r, const void* d_s, const void* d_recid, size_t n, int reject_high_s,
+                      void* d_out_xy, void* d_ok) {
+    static_assert(Field<C>::NS >= C::N, "the normalisation's prefix array holds the inverses' prefix products too");
+    const size_t L = 4 * C::N;
+    return verify_pipeline<C>(
+        ctx, n, {{ctx->ec_winv, n * L + 16}, {ctx->prefix, n * Field<C>::NS * 4}}, &d_out_xy,
+        [&](const VerifyScratch& v) {
+            launch_ecdsa_recover_prepare<C>(ctx->stream, (const uint8_t*)d_z, (const uint8_t*)d_r, (const uint8_t*)d_s,
+                                            (const uint8_t*)d_recid, n, reject_high_s, v.u1, v.u2, v.q, v.valid, (uint32_t*)ctx->prefix.p,
+                                            (uint8_t*)ctx->ec_winv.p);
+        },
+        [&](const VerifyScratch& v) { launch_ecdsa_recover_finish<C>(ctx->stream, v.xy, v.inf, v.valid, n, (uint8_t*)d_ok); });
+}
+
+int schnorr_verify_dev(ecgpu_ctx* ctx, const void* d_e, const void* d_r, const void* d_s, const void* d_p_xy, size_t n, void* d_ok) {
+    return verify_pipeline<K256Params>(
+        ctx, n, {{ctx->ec_xy, n * 64}}, &ctx->ec_xy.p,
+        [&](const VerifyScratch& v) {
+            launch_schnorr_prepare(ctx->stream, (const uint8_t*)d_e, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_p_xy, n,
+                                   v.u1, v.u2, v.q, v.valid);
+        },
+        [&](const VerifyScratch& v) { launch_schnorr_finish(ctx->stream, v.xy, v.inf, (const uint8_t*)d_r, v.valid, n, (uint8_t*)d_ok); });
+}
+
+// (from wire bytes: the prepare kernel splits the signatures and leaves r in ec_r for the finish kernel)
+int schnorr_verify_raw_dev(ecgpu_ctx* ctx, const void* d_pk_x, const void* d_msgs, size_t msg_len, const void* d_sigs, size_t n,
+                           void* d_ok) {
+    return verify_pipeline<K256Params>(
+        ctx, n, {{ctx->ec_xy, n * 64}, {ctx->ec_r, n * 32}}, &ctx->ec_xy.p,
+        [&](const VerifyScratch& v) {
+            launch_schnorr_prepare_raw(ctx->stream, (const uint8_t*)d_pk_x, (const uint8_t*)d_msgs, msg_len, (const uint8_t*)d_sigs, n, v.u1,
+                                       v.u2, v.q, (uint8_t*)ctx->ec_r.p, v.valid);
+        },
+        [&](const VerifyScratch& v) {
+            launch_schnorr_finish(ctx->stream, v.xy, v.inf, (const uint8_t*)ctx->ec_r.p, v.valid, n, (uint8_t*)d_ok);
+        });
+}
+
+int sm2dsa_verify_dev(ecgpu_ctx* ctx, const void* d_e, const void* d_r, const void* d_s, const void* d_q_xy, size_t n, void* d_ok) {
+    return verify_pipeline<Sm2Params>(
+        ctx, n, {{ctx->ec_xy, n * 64}}, &ctx->ec_xy.p,
+        [&](const VerifyScratch& v) {
+            launch_sm2dsa_prepare(ctx->stream, (const uint8_t*)d_r, (const uint8_t*)d_s, (const uint8_t*)d_q_xy, n, v.u1, v.u2, v.q, v.valid);
+        },
+        [&](const VerifyScratch& v) {
+            launch_sm2dsa_finish(ctx->stream, (const uint8_t*)d_e, v.xy, v.inf, (const uint8_t*)d_r, v.valid, n, (uint8_t*)d_ok);
+        });
+}
+
+// d_h: 32-byte hashes; d_sigs: 48-byte signatures S0 || S1
+int bign_verify_dev(ecgpu_ctx* ctx, const void* d_h, const void* d_sigs, const void* d_q_xy, size_t n, void* d_ok) {
+    return verify_pipeline<Bign256Params>(
+        ctx, n, {{ctx->ec_xy, n * 64}}, &ctx->ec_xy.p,
+        [&](const VerifyScratch& v) {
+            launch_bign_prepare(ctx->stream, (const uint8_t*)d_h, (const uint8_t*)d_sigs, (const uint8_t*)d_q_xy, n, v.u1, v.u2, v.q, v.valid);
+        },
+        [&](const VerifyScratch& v) {
+            launch_bign_finish(ctx->stream, (const uint8_t*)d_h, v.xy, v.inf, (const uint8_t*)d_sigs, v.valid, n, (uint8_t*)d_ok);
+        });
+}
+
+// The one front stage of the message-level verifiers (the counterpart of `decoded`): the hash kernel `hash()` writes the prehash
+// form into the scratch reserved here; the frame is opened before it, so the MSM lanes are joined before it reads the caller's
+// messages; the scheme's pipeline `then()` runs as the second stage, under KeepStatus.
+template <class Hash, class Then>
+int hashed(ecgpu_ctx* ctx, std::initializer_list<Reserve> bufs, Hash&& hash, Then&& then) {
+    DevCall front(ctx, 0, bufs);
+    if (front.rc != ECGPU_OK) return front.rc;
+    hash();
+    KeepStatus keep(ctx);
+    return then();
 }
 }  // namespace
 
@@ -2065,12 +2153,10 @@ int ecgpu_ecdsa_verify_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_z, con
     if (int rc = dev_args(ctx, __func__, n, {{d_z, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}},
                           false, not_ecdsa(curve))) return rc;
     return dispatch(curve, [&](auto c) {
-        return verify_dev<decltype(c)>(ctx, VERIFY_ECDSA, d_z, d_r, d_s, d_q_xy, n, reject_high_s, d_ok);
+        return ecdsa_verify_dev<decltype(c)>(ctx, d_z, d_r, d_s, d_q_xy, n, reject_high_s, d_ok);
     });
 }
 
-// (the three message-level verifiers: the hash kernel is a front stage of the call — the frame is opened before it, so the MSM
-// lanes are joined before it reads the caller's messages, and verify_dev runs as the second stage, under KeepStatus)
 int ecgpu_ecdsa_verify_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_q_xy, const void* d_msgs, size_t msg_len,
                                      const void* d_sigs, size_t n, int reject_high_s, void* d_ok) {
     // Verifier::verify(msg, sig): the curve's digest on the device, z = bits2field(digest), then the prehash path.  See ecgpu_ecdsa.h.
@@ -2080,12 +2166,12 @@ int ecgpu_ecdsa_verify_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_q_
         using C = decltype(c);
         if (n == 0) return (int)ECGPU_OK;
         const size_t L = WireBytes<C>::value;
-        DevCall front(ctx, 0, {{ctx->ec_e, n * L + 16}, {ctx->ec_r, n * L + 16}, {ctx->ec_s, n * L + 16}});
-        if (front.rc != ECGPU_OK) return front.rc;
-        launch_ecdsa_hash_msg<C>(ctx->stream, (const uint8_t*)d_msgs, msg_len, (const uint8_t*)d_sigs, n, (uint8_t*)ctx->ec_e.p,
-                                 (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
-        KeepStatus keep(ctx);
-        return verify_dev<C>(ctx, VERIFY_ECDSA, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, reject_high_s, d_ok);
+        return hashed(ctx, {{ctx->ec_e, n * L + 16}, {ctx->ec_r, n * L + 16}, {ctx->ec_s, n * L + 16}},
+                      [&] {
+                          launch_ecdsa_hash_msg<C>(ctx->stream, (const uint8_t*)d_msgs, msg_len, (const uint8_t*)d_sigs, n,
+                                                   (uint8_t*)ctx->ec_e.p, (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
+                      },
+                      [&] { return ecdsa_verify_dev<C>(ctx, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, reject_high_s, d_ok); });
     });
 }
 
@@ -2095,7 +2181,7 @@ int ecgpu_ecdsa_recover_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_z, co
     if (int rc = dev_args(ctx, __func__, n, {{d_z, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_recid, NEED},
                                              {d_out_xy, NEED | A16}, {d_ok, NEED}}, false, not_ecdsa(curve))) return rc;
     return dispatch(curve, [&](auto c) {
-        return verify_dev<decltype(c)>(ctx, VERIFY_RECOVER, d_z, d_r, d_s, d_recid, n, reject_high_s, d_ok, 0, d_out_xy);
+        return ecdsa_recover_dev<decltype(c)>(ctx, d_z, d_r, d_s, d_recid, n, reject_high_s, d_out_xy, d_ok);
     });
 }
 
@@ -2104,7 +2190,7 @@ int ecgpu_sm2dsa_verify_batch_dev(ecgpu_ctx* ctx, const void* d_e, const void* d
     // SM2DSA on the prehash: t = r + s, (x1, y1) = s G + t Q, ok = (e + x1 mod n == r).  See ecgpu_ecdsa.h.
     if (int rc = dev_args(ctx, __func__, n, {{d_e, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}}))
         return rc;
-    return verify_dev<Sm2Params>(ctx, VERIFY_SM2DSA, d_e, d_r, d_s, d_q_xy, n, 0, d_ok);
+    return sm2dsa_verify_dev(ctx, d_e, d_r, d_s, d_q_xy, n, d_ok);
 }
 
 int ecgpu_sm2dsa_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_distid, size_t distid_len, const void* d_q_xy, const void* d_msgs,
@@ -2113,18 +2199,19 @@ int ecgpu_sm2dsa_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_distid, size
     if (int rc = dev_args(ctx, __func__, n, {{d_distid, distid_len ? NEED : OPT}, {d_q_xy, NEED | A16}, {d_msgs, msg_len ? NEED : OPT},
                                              {d_sigs, NEED | A16}, {d_ok, NEED}}, distid_len > 8191)) return rc;
     if (n == 0) return ECGPU_OK;
-    DevCall front(ctx, 0, {{ctx->ec_e, n * 32}, {ctx->ec_r, n * 32}, {ctx->ec_s, n * 32}});
-    if (front.rc != ECGPU_OK) return front.rc;
-    launch_sm2dsa_hash_msg(ctx->stream, (const uint8_t*)d_distid, distid_len, (const uint8_t*)d_q_xy, (const uint8_t*)d_msgs, msg_len,
-                           (const uint8_t*)d_sigs, n, (uint8_t*)ctx->ec_e.p, (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
-    KeepStatus keep(ctx);
-    return verify_dev<Sm2Params>(ctx, VERIFY_SM2DSA, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, 0, d_ok);
+    return hashed(ctx, {{ctx->ec_e, n * 32}, {ctx->ec_r, n * 32}, {ctx->ec_s, n * 32}},
+                  [&] {
+                      launch_sm2dsa_hash_msg(ctx->stream, (const uint8_t*)d_distid, distid_len, (const uint8_t*)d_q_xy,
+                                             (const uint8_t*)d_msgs, msg_len, (const uint8_t*)d_sigs, n, (uint8_t*)ctx->ec_e.p,
+                                             (uint8_t*)ctx->ec_r.p, (uint8_t*)ctx->ec_s.p);
+                  },
+                  [&] { return sm2dsa_verify_dev(ctx, ctx->ec_e.p, ctx->ec_r.p, ctx->ec_s.p, d_q_xy, n, d_ok); });
 }
 
 int ecgpu_bign_verify_batch_dev(ecgpu_ctx* ctx, const void* d_h, const void* d_sigs, const void* d_q_xy, size_t n, void* d_ok) {
     // bign on the prehash: R = ((S1 + H) mod q) G + (S0 + 2^128) Q, ok = (S0 == belt-hash(OID || x(R) || H)[..16]).  See ecgpu_ecdsa.h.
     if (int rc = dev_args(ctx, __func__, n, {{d_h, NEED | A16}, {d_sigs, NEED | A16}, {d_q_xy, NEED | A16}, {d_ok, NEED}})) return rc;
-    return verify_dev<Bign256Params>(ctx, VERIFY_BIGN, d_h, nullptr, d_sigs, d_q_xy, n, 0, d_ok);
+    return bign_verify_dev(ctx, d_h, d_sigs, d_q_xy, n, d_ok);
 }
 
 int ecgpu_bign_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_q_xy, const void* d_msgs, size_t msg_len, const void* d_sigs, size_t n,
@@ -2133,11 +2220,9 @@ int ecgpu_bign_verify_msg_batch_dev(ecgpu_ctx* ctx, const void* d_q_xy, const vo
     if (int rc = dev_args(ctx, __func__, n, {{d_q_xy, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_sigs, NEED | A16}, {d_ok, NEED}}))
         return rc;
     if (n == 0) return ECGPU_OK;
-    DevCall front(ctx, 0, {{ctx->ec_e, n * 32}});
-    if (front.rc != ECGPU_OK) return front.rc;
-    launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)ctx->ec_e.p);
-    KeepStatus keep(ctx);
-    return verify_dev<Bign256Params>(ctx, VERIFY_BIGN, ctx->ec_e.p, nullptr, d_sigs, d_q_xy, n, 0, d_ok);
+    return hashed(ctx, {{ctx->ec_e, n * 32}},
+                  [&] { launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)ctx->ec_e.p); },
+                  [&] { return bign_verify_dev(ctx, ctx->ec_e.p, d_sigs, d_q_xy, n, d_ok); });
 }
 
 int ecgpu_schnorr_verify_batch_dev(ecgpu_ctx* ctx, const void* d_e, const void* d_r, const void* d_s, const void* d_p_xy,
@@ -2145,7 +2230,7 @@ int ecgpu_schnorr_verify_batch_dev(ecgpu_ctx* ctx, const void* d_e, const void* 
     // BIP340 over secp256k1: R = s G - e P, ok = R finite, y(R) even, x(R) == r.  See ecgpu_ecdsa.h.
     if (int rc = dev_args(ctx, __func__, n, {{d_e, NEED | A16}, {d_r, NEED | A16}, {d_s, NEED | A16}, {d_p_xy, NEED | A16}, {d_ok, NEED}}))
         return rc;
-    return verify_dev<K256Params>(ctx, VERIFY_SCHNORR, d_e, d_r, d_s, d_p_xy, n, 0, d_ok);
+    return schnorr_verify_dev(ctx, d_e, d_r, d_s, d_p_xy, n, d_ok);
 }
 
 int ecgpu_schnorr_verify_raw_batch_dev(ecgpu_ctx* ctx, const void* d_pk_x, const void* d_msgs, size_t msg_len, const void* d_sigs,
@@ -2153,10 +2238,10 @@ int ecgpu_schnorr_verify_raw_batch_dev(ecgpu_ctx* ctx, const void* d_pk_x, const
     // VerifyingKey::from_bytes(pk)?.verify_raw(msg, sig) from wire bytes: lift_x, challenge hash, s G - e P.  See ecgpu_ecdsa.h.
     if (int rc = dev_args(ctx, __func__, n, {{d_pk_x, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_sigs, NEED | A16}, {d_ok, NEED}}))
         return rc;
-    return verify_dev<K256Params>(ctx, VERIFY_SCHNORR_RAW, d_msgs, nullptr, d_sigs, d_pk_x, n, 0, d_ok, msg_len);
+    return schnorr_verify_raw_dev(ctx, d_pk_x, d_msgs, msg_len, d_sigs, n, d_ok);
 }
 
-// ---- signing (ecgpu_sign.h): the entry points around ecdsa_sign_dev ----
+// ---- signing (ecgpu_sign.h): the entry points around ecdsa_sign_dev and schnorr_sign_dev ----
 // every argument is checked before anything is queued.  from_msg: d_z is the message array (NULL allowed when msg_len == 0); a
 // nonce array is alignment-checked whenever there is one
 static int ecdsa_sign_entry(ecgpu_ctx* ctx, const char* fn, int curve, bool rfc6979, const void* d_d, const void* d_k, const void* d_z,
@@ -2190,31 +2275,9 @@ int ecgpu_ecdsa_sign_msg_batch_dev(ecgpu_ctx* ctx, int curve, const void* d_d, c
 int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_t msg_len, const void* d_aux_rand,
                                      size_t n, void* d_out_sig, void* d_ok) {
     // `SigningKey::sign_raw(msg, aux_rand)` with the key fix-up: P = d G, the nonce hashes, R = k G, s = k + e d.  See ecgpu_sign.h.
-    using C = K256Params;
-    constexpr int NS = Field<C>::NS;
-    int rc;
-    if ((rc = dev_args(ctx, __func__, n, {{d_sk, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_aux_rand, NEED | A16}, {d_out_sig, NEED | A16},
-                                          {d_ok, NEED}})) != ECGPU_OK) return rc;
-    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
-    if (n == 0) return ECGPU_OK;
-    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
-                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
-                  {ctx->sg_dp, n * 64 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}});
-    if (call.rc != ECGPU_OK) return call.rc;
-    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *dp = (uint8_t*)ctx->sg_dp.p;
-    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
-    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
-    call.mark(0);
-    launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_sk, n, k, flag);                   // d, or 1 in place of an unusable key
-    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // P = d G
-    launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n, dp, k, flag);
-    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
-    launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
-    call.mark(2);
-    return call.done();
+    if (int rc = dev_args(ctx, __func__, n, {{d_sk, NEED | A16}, {d_msgs, msg_len ? NEED : OPT}, {d_aux_rand, NEED | A16}, {d_out_sig, NEED | A16},
+                                             {d_ok, NEED}})) return rc;
+    return schnorr_sign_dev(ctx, d_sk, d_msgs, msg_len, d_aux_rand, n, d_out_sig, d_ok);
 }
 
 static int ecdh_dev(ecgpu_ctx* ctx, int curve, const void* d_scalars, const void* d_points_xy, size_t n, void* d_out_x, void* d_ok,

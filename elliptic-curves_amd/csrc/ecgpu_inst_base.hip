@@ -105,15 +105,6 @@ template <> void launch_ecdsa_prepare<CurveT>(hipStream_t s, const uint8_t* z, c
     hipLaunchKernelGGL(k_ecdsa_prepare<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, z, r, sig_s, q_xy, n, reject_high_s, u1, u2,
                        q_out, valid, batch ? (const uint8_t*)inv_out : (const uint8_t*)nullptr);
 }
-template <> void launch_schnorr_prepare<CurveT>(hipStream_t s, const uint8_t* e, const uint8_t* r, const uint8_t* sig_s,
-                                                const uint8_t* p_xy, size_t n, uint8_t* a, uint8_t* b, uint8_t* q_out,
-                                                uint8_t* valid) {
-    hipLaunchKernelGGL(k_schnorr_prepare<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, e, r, sig_s, p_xy, n, a, b, q_out, valid);
-}
-template <> void launch_schnorr_finish<CurveT>(hipStream_t s, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r,
-                                               const uint8_t* valid, size_t n, uint8_t* ok) {
-    hipLaunchKernelGGL(k_schnorr_finish<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, r_xy, r_inf, r, valid, n, ok);
-}
 template <> void launch_extract_x<CurveT>(hipStream_t s, const uint8_t* xy, const uint8_t* inf, size_t n, uint8_t* out_x,
                                           uint8_t* ok) {
     hipLaunchKernelGGL(k_extract_x<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, xy, inf, n, out_x, ok);
@@ -146,14 +137,6 @@ template <> void launch_ecdsa_recover_prepare<CurveT>(hipStream_t s, const uint8
 template <> void launch_ecdsa_recover_finish<CurveT>(hipStream_t s, uint8_t* xy, const uint8_t* inf, const uint8_t* valid, size_t n,
                                                      uint8_t* ok) {
     hipLaunchKernelGGL(k_ecdsa_recover_finish<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, xy, inf, valid, n, ok);
-}
-template <> void launch_sm2dsa_prepare<CurveT>(hipStream_t s, const uint8_t* r, const uint8_t* sig_s, const uint8_t* q_xy, size_t n,
-                                               uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* valid) {
-    hipLaunchKernelGGL(k_sm2dsa_prepare<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, r, sig_s, q_xy, n, a, b, q_out, valid);
-}
-template <> void launch_sm2dsa_finish<CurveT>(hipStream_t s, const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf,
-                                              const uint8_t* r, const uint8_t* valid, size_t n, uint8_t* ok) {
-    hipLaunchKernelGGL(k_sm2dsa_finish<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, e, r_xy, r_inf, r, valid, n, ok);
 }
 template <> void launch_selftest_field<CurveT>(hipStream_t s, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out,
                                                int* status) {

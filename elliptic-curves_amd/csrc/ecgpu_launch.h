@@ -1,6 +1,6 @@
-// ecgpu_launch.h — host-side launch wrappers, one explicit instantiation per curve.
-// The kernels are large fully-inlined bodies; each (kernel group x curve) is its own translation
-// unit (ecgpu_inst_*.hip compiled with -DECGPU_CURVE=...) so the build parallelises.
+// ecgpu_launch.h — host-side launch wrappers: templates with one explicit instantiation per curve, and plain
+// functions (ecgpu_misc.hip) for what exists on one curve only.  The kernels are large fully-inlined bodies; each
+// (kernel group x curve) is its own translation unit (ecgpu_inst_*.hip compiled with -DECGPU_CURVE=...) so the build parallelises.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -75,14 +75,6 @@ template <class C> void launch_ecdsa_recover_prepare(hipStream_t s, const uint8_
                                                      uint8_t* inv_out = nullptr);
 template <class C> void launch_ecdsa_recover_finish(hipStream_t s, uint8_t* xy, const uint8_t* inf, const uint8_t* valid, size_t n,
                                                     uint8_t* ok);
-template <class C> void launch_sm2dsa_prepare(hipStream_t s, const uint8_t* r, const uint8_t* sig_s, const uint8_t* q_xy, size_t n, uint8_t* a,
-                                              uint8_t* b, uint8_t* q_out, uint8_t* valid);
-template <class C> void launch_sm2dsa_finish(hipStream_t s, const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r,
-                                             const uint8_t* valid, size_t n, uint8_t* ok);
-template <class C> void launch_schnorr_prepare(hipStream_t s, const uint8_t* e, const uint8_t* r, const uint8_t* sig_s, const uint8_t* p_xy,
-                                               size_t n, uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* valid);
-template <class C> void launch_schnorr_finish(hipStream_t s, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r,
-                                              const uint8_t* valid, size_t n, uint8_t* ok);
 template <class C> void launch_extract_x(hipStream_t s, const uint8_t* xy, const uint8_t* inf, size_t n, uint8_t* out_x, uint8_t* ok);
 template <class C> void launch_decompress(hipStream_t s, const uint8_t* xs, const uint8_t* y_is_odd, size_t n, uint8_t* out_xy,
                                           uint8_t* ok);
@@ -155,6 +147,11 @@ template <class C> void launch_msm_finish(const MsmPlan& p, hipStream_t s, const
                                           uint32_t* out, uint8_t* out_xy = nullptr, uint8_t* out_inf = nullptr);
 
 // ---- curve-independent ----
+// BIP340 verification (secp256k1 only; ecgpu_ecdsa.h)
+void launch_schnorr_prepare(hipStream_t s, const uint8_t* e, const uint8_t* r, const uint8_t* sig_s, const uint8_t* p_xy, size_t n,
+                            uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* valid);
+void launch_schnorr_finish(hipStream_t s, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r, const uint8_t* valid, size_t n,
+                           uint8_t* ok);
 void launch_schnorr_prepare_raw(hipStream_t s, const uint8_t* pk_x, const uint8_t* msgs, size_t msg_len, const uint8_t* sigs,
                                 size_t n, uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* r_out, uint8_t* valid);
 // bign verification (bign-curve256v1 only; ecgpu_ecdsa.h)
@@ -163,6 +160,11 @@ void launch_bign_prepare(hipStream_t s, const uint8_t* h, const uint8_t* sigs, c
 void launch_bign_finish(hipStream_t s, const uint8_t* h, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* sigs,
                         const uint8_t* valid, size_t n, uint8_t* ok);
 void launch_bign_hash_msg(hipStream_t s, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* h_out);
+// SM2DSA verification (sm2 only; ecgpu_ecdsa.h)
+void launch_sm2dsa_prepare(hipStream_t s, const uint8_t* r, const uint8_t* sig_s, const uint8_t* q_xy, size_t n, uint8_t* a, uint8_t* b,
+                           uint8_t* q_out, uint8_t* valid);
+void launch_sm2dsa_finish(hipStream_t s, const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r,
+                          const uint8_t* valid, size_t n, uint8_t* ok);
 void launch_sm2dsa_hash_msg(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* q_xy, const uint8_t* msgs,
                             size_t msg_len, const uint8_t* sigs, size_t n, uint8_t* e_out, uint8_t* r_out, uint8_t* s_out);
 void launch_k256_glv(hipStream_t s, const uint8_t* scalars, size_t n, uint8_t* r1, uint8_t* r2, int* status);

@@ -1,4 +1,4 @@
-// ecgpu_misc.hip — curve-independent kernels: k256 GLV split (parity probe) and VALU roof probes.
+// ecgpu_misc.hip — instantiated once: the one-curve signature schemes, k256 GLV split (parity probe), VALU roof probes.
 #include "ecgpu_kernels.h"
 #include "ecgpu_launch.h"
 #include "ecgpu_ecdsa.h"
@@ -229,12 +229,32 @@ void launch_gather_probe(hipStream_t s, const uint32_t* table, size_t entries, i
     hipLaunchKernelGGL(k_gather_probe, dim3(blocks), dim3(BLOCK), 0, s, table, entries, per_lane, out);
 }
 
+void launch_schnorr_prepare(hipStream_t s, const uint8_t* e, const uint8_t* r, const uint8_t* sig_s, const uint8_t* p_xy, size_t n,
+                            uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* valid) {
+    hipLaunchKernelGGL(k_schnorr_prepare<K256Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, e, r, sig_s, p_xy, n,
+                       a, b, q_out, valid);
+}
+void launch_schnorr_finish(hipStream_t s, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r, const uint8_t* valid, size_t n,
+                           uint8_t* ok) {
+    hipLaunchKernelGGL(k_schnorr_finish<K256Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, r_xy, r_inf, r, valid,
+                       n, ok);
+}
 void launch_schnorr_prepare_raw(hipStream_t s, const uint8_t* pk_x, const uint8_t* msgs, size_t msg_len, const uint8_t* sigs,
                                 size_t n, uint8_t* a, uint8_t* b, uint8_t* q_out, uint8_t* r_out, uint8_t* valid) {
     hipLaunchKernelGGL(k_schnorr_prepare_raw<K256Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, pk_x, msgs,
                        msg_len, sigs, n, a, b, q_out, r_out, valid);
 }
 
+void launch_sm2dsa_prepare(hipStream_t s, const uint8_t* r, const uint8_t* sig_s, const uint8_t* q_xy, size_t n, uint8_t* a, uint8_t* b,
+                           uint8_t* q_out, uint8_t* valid) {
+    hipLaunchKernelGGL(k_sm2dsa_prepare<Sm2Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, r, sig_s, q_xy, n, a, b,
+                       q_out, valid);
+}
+void launch_sm2dsa_finish(hipStream_t s, const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* r,
+                          const uint8_t* valid, size_t n, uint8_t* ok) {
+    hipLaunchKernelGGL(k_sm2dsa_finish<Sm2Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, e, r_xy, r_inf, r, valid,
+                       n, ok);
+}
 void launch_sm2dsa_hash_msg(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* q_xy, const uint8_t* msgs,
                             size_t msg_len, const uint8_t* sigs, size_t n, uint8_t* e_out, uint8_t* r_out, uint8_t* s_out) {
     hipLaunchKernelGGL(k_sm2dsa_hash_msg<Sm2Params>, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, distid, distid_len,
