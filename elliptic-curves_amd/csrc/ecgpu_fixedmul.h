@@ -18,7 +18,8 @@
 // a value < 2^(bits - 31) for the curves whose n is within 2^-4 of 2^bits (k256: 2^129, p256 / sm2: 2^225, p384: 2^190,
 // p224: 2^113, p192: 2^96), so with W <= 26 the window below the top one is zero and hands no carry up.  Contradiction.
 // The other curves (brainpoolP256r1: n = 0.66 * 2^256; p521: 521 bits in 544) do not rely on this: COMB_NEEDS_CHECK.
-// tests: comb_corner_scalars (tests/gpu_common.py) at W = 5 and 15 (top window at bit 255) and at the default widths.
+// tests: comb_corner_scalars (tests/gpu_common.py) at W = 5, 15 and 17 (top window at bit 255) and, on a table pinned to each of
+// them, at the widths in use (16, 22, the widest): tests/test_gpu_comb_table.py, which also checks the table's entries as entries.
 #pragma once
 
 #include "ecgpu_point.h"
