@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "ecgpu_ecdsa_sign_batch", "ecgpu_ecdsa_sign_batch_dev", "ecgpu_ecdsa_sign_rfc6979_batch", "ecgpu_ecdsa_sign_rfc6979_batch_dev",
     "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_sign_msg_batch_dev", "ecgpu_schnorr_sign_raw_batch", "ecgpu_schnorr_sign_raw_batch_dev",
     "ecgpu_hash_to_curve_batch", "ecgpu_encode_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_map_to_curve_batch",
+    "ecgpu_sm2_pke_encrypt_batch", "ecgpu_sm2_pke_decrypt_batch",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -727,6 +728,33 @@ class Engine:
         out, inf = np.zeros(n * 2 * L, np.uint8), np.zeros(n, np.uint8)
         self._chk(self._lib.ecgpu_map_to_curve_batch(self._ctx, curve, _hp(uu), int(per_point), ctypes.c_size_t(n), _hp(out), _hp(inf)))
         return out, inf
+
+    # ---- SM2 public-key encryption (`sm2::pke`; secret nonces, keys and messages: the uniform-schedule multiplications) ----
+    def sm2_pke_encrypt(self, pk_xy, k, msgs, msg_len):
+        """`EncryptingKey::encrypt_cipher_with_buf` with the caller's nonces: pk_xy n*64, k n*32, msgs n*msg_len bytes (one length
+        per call, at least 1); returns (c1_xy uint8[n*64], c2 uint8[n*msg_len], c3 uint8[n*32], ok uint8[n]).  ok = 0 (k outside
+        [1, n), a bad key, an all-zero keystream) leaves zero records: draw another k for that element."""
+        pp, kk = _host(pk_xy), _host(k)
+        mm = _host(msgs) if msg_len else None
+        n = kk.size // 32
+        _need("pk_xy", pp, n * 64); _need("k", kk, n * 32); _need("msgs", mm, n * msg_len)
+        c1, c2, c3, ok = np.zeros(n * 64, np.uint8), np.zeros(n * msg_len, np.uint8), np.zeros(n * 32, np.uint8), np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_sm2_pke_encrypt_batch(self._ctx, _hp(pp), _hp(kk), _hp(mm), ctypes.c_size_t(msg_len), ctypes.c_size_t(n),
+                                                        _hp(c1), _hp(c2) if msg_len else None, _hp(c3), _hp(ok)))
+        return c1, c2, c3, ok
+
+    def sm2_pke_decrypt(self, d, c1_xy, c2, msg_len, c3):
+        """`DecryptingKey::decrypt_cipher_with_buf` on split ciphertexts: d n*32 (one key per element), c1_xy n*64, c2 n*msg_len
+        (0 allowed), c3 n*32; returns (msgs uint8[n*msg_len], ok uint8[n]).  ok = 0 (d outside [1, n), C1 off the curve, C3 does
+        not match) leaves a zero record."""
+        dd, pp, hh = _host(d), _host(c1_xy), _host(c3)
+        cc = _host(c2) if msg_len else None
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("c1_xy", pp, n * 64); _need("c2", cc, n * msg_len); _need("c3", hh, n * 32)
+        out, ok = np.zeros(n * msg_len, np.uint8), np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_sm2_pke_decrypt_batch(self._ctx, _hp(dd), _hp(pp), _hp(cc), ctypes.c_size_t(msg_len), _hp(hh),
+                                                        ctypes.c_size_t(n), _hp(out) if msg_len else None, _hp(ok)))
+        return out, ok
 
     def decompress(self, curve, xs, y_is_odd):
         """DecompressPoint::decompress for a batch: returns (xy uint8[n*2L], ok uint8[n])."""

@@ -34,6 +34,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
     size_t dirty = 0;         // bytes from the start that calls have asked for since the buffer was last wiped (wipe_scratch zeroes these, not cap)
+    size_t used = 0;          // the most any call has asked for (never reset): beyond it the allocation was never written by this context
 };
 
 // A context's view of a basepoint comb table.  The table itself is owned by the per-device registry below and shared by
@@ -102,6 +103,7 @@ struct ecgpu_ctx {
     DevBuf sg_k, sg_flag, sg_state, sg_dp;   // signing: the nonces handed to k_fixed_base_ct, their verdicts, the RFC 6979 generator's
                                  // K / V state between its two kernels, the fixed-up Schnorr key d' || x(P) — all wiped behind the call
     DevBuf out2;                 // a third staged output (the recovery ids of the host-pointer signing calls)
+    DevBuf out3;                 // a fourth (ecgpu_sm2_pke_encrypt_batch: C1, C2, C3 and ok)
     int rfc6979_cap = 128;       // candidates the RFC 6979 generator tries per element; lowered by the tests only
                                  // (ecgpu_testhook_rfc6979_max_candidates, this context alone)
     DevBuf cx_xy, cx_inf;        // x || y + flag records decoded from compressed input (ecgpu_msm_compressed, ecgpu_batch_mul_compressed)
@@ -147,6 +149,7 @@ namespace {
 // it is used on (the context's own, or an MSM lane's)
 int ensure_on(ecgpu_ctx* ctx, hipStream_t stream, DevBuf& b, size_t bytes) {
     if (bytes > b.dirty) b.dirty = bytes;
+    if (bytes > b.used) b.used = bytes;
     if (bytes <= b.cap) return ECGPU_OK;
     if (b.p) {
         HIP_TRY(ctx, hipStreamSynchronize(stream));
@@ -751,6 +754,49 @@ int schnorr_sign_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_
     call.mark(1);
     if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
     launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
+    call.mark(2);
+    return call.done();
+}
+
+// ---- SM2 public-key encryption (ecgpu_pke.h): the frame and the steps of ecdsa_sign_dev ----------------------------------------
+// seal (encrypt): d_scalar = k, d_point = P_B, d_in = M; C1 = k G is normalised straight into the caller's array (a public point),
+// (x2, y2) = k P_B into ec_xy, k_pke_seal writes C2 = d_out, C3 = d_c3 and ok (and zeroes the C1 of an element without a verdict).
+// open (decrypt): d_scalar = d, d_point = C1, d_in = C2, d_c3 = the ciphertext's C3, M' = d_out; no fixed-base leg.
+// The sanitised scalar lives in sg_k, the sanitised point in sg_dp, the verdict bytes in sg_flag, x2 || y2 in ec_xy: every buffer that
+// holds k, d, x2 || y2 or anything derived from them is in the reserve list and is wiped in stream order whatever way the call leaves
+// (the staged copies of k, d and the messages are the host-pointer entry points' to mark).  There is no public `_dev` form of these
+// calls: every chunk of a host-pointer call reaches this function through `staged`.
+int sm2_pke_dev(ecgpu_ctx* ctx, bool open, const void* d_scalar, const void* d_point, const void* d_in, size_t msg_len, size_t n,
+                void* d_c1, void* d_out, void* d_c3, void* d_ok) {
+    using C = Sm2Params;
+    constexpr int NS = Field<C>::NS;
+    int rc;
+    if (!open && (rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    const size_t tstride = var_base_slots<C>(n);
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->vtab, tstride * var_base_tab_words<C>() * 4}, {ctx->ct_flags, n + 16},
+                  {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16}, {ctx->sg_dp, n * 64 + 16}, {ctx->ec_xy, n * 64 + 16},
+                  {ctx->ec_inf, n + 16}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *pt = (uint8_t*)ctx->sg_dp.p;
+    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
+    call.mark(0);
+    launch_pke_load<C>(ctx->stream, (const uint8_t*)d_scalar, (const uint8_t*)d_point, n, k, pt, flag);
+    if (!open) {
+        launch_fixed_base_ct<C>(ctx->stream, k, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p,
+                                ctx->d_status);
+        if ((rc = normalize_out<C>(ctx, n, d_c1, inf)) != ECGPU_OK) return rc;                   // C1 = k G
+    }
+    launch_var_base_ct<C>(ctx->stream, k, pt, nullptr, n, (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p,
+                          (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    call.mark(1);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // (x2, y2) = k P_B resp. d C1
+    if (open)
+        launch_pke_open<C>(ctx->stream, xy, flag, (const uint8_t*)d_in, msg_len, (const uint8_t*)d_c3, n, (uint8_t*)d_out, (uint8_t*)d_ok);
+    else
+        launch_pke_seal<C>(ctx->stream, xy, flag, (const uint8_t*)d_in, msg_len, n, (uint8_t*)d_c1, (uint8_t*)d_out, (uint8_t*)d_c3,
+                           (uint8_t*)d_ok);
     call.mark(2);
     return call.done();
 }
@@ -1697,7 +1743,8 @@ void ecgpu_destroy(ecgpu_ctx* ctx) {
                       &ctx->out0, &ctx->out1, &ctx->msm_ws, &ctx->ec_u1, &ctx->ec_u2, &ctx->ec_winv, &ctx->ec_q, &ctx->ec_valid, &ctx->ec_xy,
                       &ctx->ec_inf, &ctx->ec_r, &ctx->ec_e, &ctx->ec_s, &ctx->ec_id})
         if (b->p) (void)hipFree(b->p);
-    for (DevBuf* b : {&ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp, &ctx->out2})
+    for (DevBuf* b : {&ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp, &ctx->out2,
+                      &ctx->out3})
         if (b->p) (void)hipFree(b->p);
     for (auto& l : ctx->lane) {
         if (l.s) (void)hipStreamSynchronize(l.s);
@@ -1895,7 +1942,7 @@ int ecgpu_wipe(ecgpu_ctx* ctx) {
     for (DevBuf* b : {&ctx->proj, &ctx->prefix, &ctx->vtab, &ctx->bases, &ctx->in0, &ctx->in1, &ctx->in2, &ctx->in3, &ctx->out0, &ctx->out1,
                       &ctx->msm_ws, &ctx->ec_u1, &ctx->ec_u2, &ctx->ec_winv, &ctx->ec_q, &ctx->ec_valid, &ctx->ec_xy, &ctx->ec_inf, &ctx->ec_r, &ctx->ec_e,
                       &ctx->ec_s, &ctx->ec_id, &ctx->ct_flags, &ctx->cx_xy, &ctx->cx_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp,
-                      &ctx->out2})
+                      &ctx->out2, &ctx->out3})
         if (b->p) HIP_TRY(ctx, hipMemsetAsync(b->p, 0, b->cap, ctx->stream));
     for (auto& l : ctx->lane)
         for (DevBuf* b : {&l.ws, &l.proj, &l.prefix, &l.cx_xy, &l.cx_inf})
@@ -1908,6 +1955,25 @@ int ecgpu_wipe(ecgpu_ctx* ctx) {
 // restores 128
 void ecgpu_testhook_rfc6979_max_candidates(ecgpu_ctx* ctx, int cap) {
     if (ctx) ctx->rfc6979_cap = cap >= 1 && cap <= 128 ? cap : 128;
+}
+
+// test-only (not in include/ecgpu.h): the bytes that are not zero in the buffers the secret-scalar calls wipe behind themselves
+// (wipe_scratch's sets and the staging buffers a host-pointer call marks SECRET), over everything a call ever asked of them (the
+// headroom of an allocation beyond that was never written by this context and is not its to vouch for); -1 on a failed copy.
+// tests/test_gpu_pke.py reads it after an encryption and after a decryption.
+long long ecgpu_testhook_wiped_scratch_nonzero(ecgpu_ctx* ctx) {
+    if (!check_ctx(ctx) || hipStreamSynchronize(ctx->stream) != hipSuccess) return -1;
+    long long count = 0;
+    std::vector<uint8_t> host;
+    for (DevBuf* b : {&ctx->proj, &ctx->prefix, &ctx->ec_xy, &ctx->ec_inf, &ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp,
+                      &ctx->ct_flags, &ctx->in0, &ctx->in3, &ctx->out0, &ctx->out1}) {
+        const size_t len = b->used < b->cap ? b->used : b->cap;
+        if (!b->p || !len) continue;
+        host.resize(len);
+        if (hipMemcpy(host.data(), b->p, len, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+        for (uint8_t v : host) count += v != 0;
+    }
+    return count;
 }
 
 // test-only (not in include/ecgpu.h): comb tables above `mb` MiB are refused as if the allocation had failed; 0 switches it off
@@ -2597,6 +2663,30 @@ int ecgpu_schnorr_sign_raw_batch(ecgpu_ctx* ctx, const uint8_t* sk, const uint8_
     return staged(ctx, n, {{sk, &ctx->in0, 32, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {aux_rand, &ctx->in3, 32, SECRET}},
                   {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
                       return ecgpu_schnorr_sign_raw_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0], out[1]);
+                  });
+}
+
+// ---- SM2 public-key encryption: k, d and the messages are staged as secrets; C1, C2 and C3 are public ----
+// (host-pointer forms only: sm2_pke_dev is internal, every chunk reaches it through `staged`)
+int ecgpu_sm2_pke_encrypt_batch(ecgpu_ctx* ctx, const uint8_t* pk_xy, const uint8_t* k, const uint8_t* msgs, size_t msg_len, size_t n,
+                                uint8_t* out_c1_xy, uint8_t* out_c2, uint8_t* out_c3, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(msg_len == 0 || msg_len > 0xFFFFFFFFull || (n && (!pk_xy || !k || !msgs || !out_c1_xy || !out_c2 || !out_c3 || !ok)))) return h.rc;
+    return staged(ctx, n, {{pk_xy, &ctx->in1, 64}, {k, &ctx->in0, 32, SECRET}, {msgs, &ctx->in3, msg_len, SECRET}},
+                  {{out_c1_xy, &ctx->out0, 64}, {out_c2, &ctx->out1, msg_len}, {out_c3, &ctx->out2, 32}, {ok, &ctx->out3, 1}},
+                  [&](auto in, auto out, size_t m) {
+                      return sm2_pke_dev(ctx, false, in[1], in[0], in[2], msg_len, m, out[0], out[1], out[2], out[3]);
+                  });
+}
+
+int ecgpu_sm2_pke_decrypt_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* c1_xy, const uint8_t* c2, size_t msg_len, const uint8_t* c3,
+                                size_t n, uint8_t* out_msgs, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(msg_len > 0xFFFFFFFFull || (n && (!d || !c1_xy || !c3 || !ok || (msg_len && (!c2 || !out_msgs)))))) return h.rc;
+    // (msg_len == 0: nothing to stage for C2 and M'; the kernel touches neither and the verdict is SM3(x2 || y2) == C3)
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {c1_xy, &ctx->in1, 64}, {msg_len ? c2 : nullptr, &ctx->in2, msg_len}, {c3, &ctx->in3, 32}},
+                  {{msg_len ? out_msgs : nullptr, &ctx->out0, msg_len, SECRET}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return sm2_pke_dev(ctx, true, in[0], in[1], in[2], msg_len, m, nullptr, out[0], const_cast<void*>(in[3]), out[1]);
                   });
 }
 

@@ -1,6 +1,7 @@
 // ecgpu_inst_sign.hip — instantiates the signing kernels (ecgpu_sign.h) for -DECGPU_CURVE=...; a translation unit of its own so
 // that tools/ct_isa_check.py --unit sign can look at exactly these kernels, and so that the HMAC bodies build beside the rest
 #include "ecgpu_sign.h"
+#include "ecgpu_pke.h"
 #include "ecgpu_launch.h"
 
 namespace ecgpu {
@@ -23,6 +24,28 @@ void schnorr_finish_impl(hipStream_t s, const uint8_t* dp, const uint8_t* k, con
     if constexpr (C::ID == CURVE_K256)
         hipLaunchKernelGGL(k_schnorr_sign_finish<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, dp, k, flag, r_xy, r_inf, msgs, msg_len, n,
                            sig, ok);
+}
+
+// SM2 public-key encryption exists over the sm2 curve with SM3 only (ecgpu_pke.h): the other curves' translation units hold none of
+// its kernels
+template <class C>
+void pke_load_impl(hipStream_t s, const uint8_t* s_in, const uint8_t* xy_in, size_t n, uint8_t* s_out, uint8_t* xy_out, uint8_t* flag) {
+    if constexpr (C::ID == CURVE_SM2) {
+        hipLaunchKernelGGL(k_pke_load<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, s_in, n, s_out, flag);
+        hipLaunchKernelGGL(k_pke_point<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, xy_in, n, xy_out, flag);
+    }
+}
+template <class C>
+void pke_seal_impl(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* c1,
+                   uint8_t* c2, uint8_t* c3, uint8_t* ok) {
+    if constexpr (C::ID == CURVE_SM2)
+        hipLaunchKernelGGL(k_pke_seal<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, x2y2, flag, msgs, msg_len, n, c1, c2, c3, ok);
+}
+template <class C>
+void pke_open_impl(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* c2, size_t msg_len, const uint8_t* c3,
+                   size_t n, uint8_t* msgs_out, uint8_t* ok) {
+    if constexpr (C::ID == CURVE_SM2)
+        hipLaunchKernelGGL(k_pke_open<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, x2y2, flag, c2, msg_len, c3, n, msgs_out, ok);
 }
 }  // namespace
 
@@ -54,6 +77,18 @@ template <> void launch_schnorr_sign_finish<CurveT>(hipStream_t s, const uint8_t
                                                     const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len,
                                                     size_t n, uint8_t* sig, uint8_t* ok) {
     schnorr_finish_impl<CurveT>(s, dp, k, flag, r_xy, r_inf, msgs, msg_len, n, sig, ok);
+}
+template <> void launch_pke_load<CurveT>(hipStream_t s, const uint8_t* s_in, const uint8_t* xy_in, size_t n, uint8_t* s_out,
+                                         uint8_t* xy_out, uint8_t* flag) {
+    pke_load_impl<CurveT>(s, s_in, xy_in, n, s_out, xy_out, flag);
+}
+template <> void launch_pke_seal<CurveT>(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* msgs, size_t msg_len,
+                                         size_t n, uint8_t* c1, uint8_t* c2, uint8_t* c3, uint8_t* ok) {
+    pke_seal_impl<CurveT>(s, x2y2, flag, msgs, msg_len, n, c1, c2, c3, ok);
+}
+template <> void launch_pke_open<CurveT>(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* c2, size_t msg_len,
+                                         const uint8_t* c3, size_t n, uint8_t* msgs_out, uint8_t* ok) {
+    pke_open_impl<CurveT>(s, x2y2, flag, c2, msg_len, c3, n, msgs_out, ok);
 }
 
 }  // namespace ecgpu

@@ -120,6 +120,14 @@ template <class C> void launch_schnorr_nonce(hipStream_t s, const uint8_t* sk, c
 template <class C> void launch_schnorr_sign_finish(hipStream_t s, const uint8_t* dp, const uint8_t* k, const uint8_t* flag,
                                                    const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len, size_t n,
                                                    uint8_t* sig, uint8_t* ok);
+// SM2 public-key encryption (ecgpu_pke.h; launches nothing for a curve other than sm2).  load: the secret scalar (k or d) and the
+// public point (P_B or C1) sanitised, one verdict byte; seal / open: everything after the multiplications
+template <class C> void launch_pke_load(hipStream_t s, const uint8_t* s_in, const uint8_t* xy_in, size_t n, uint8_t* s_out, uint8_t* xy_out,
+                                        uint8_t* flag);
+template <class C> void launch_pke_seal(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* msgs, size_t msg_len, size_t n,
+                                        uint8_t* c1, uint8_t* c2, uint8_t* c3, uint8_t* ok);
+template <class C> void launch_pke_open(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* c2, size_t msg_len,
+                                        const uint8_t* c3, size_t n, uint8_t* msgs_out, uint8_t* ok);
 
 // ---- group "h2c": RFC 9380 hash-to-curve (ecgpu_h2c.h); k256, p256 and p384 only (h2c_supported), nothing is launched for the others ----
 template <class C> bool h2c_supported();

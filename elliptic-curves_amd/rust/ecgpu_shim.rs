@@ -42,8 +42,9 @@ use std::sync::{LazyLock, Mutex};
 
 use elliptic_curve::{
     point::AffineCoordinates,
-    sec1::{FromSec1Point, ModulusSize, Sec1Point},
-    CurveArithmetic, FieldBytes, PrimeField,
+    rand_core::TryCryptoRng,
+    sec1::{FromSec1Point, ModulusSize, Sec1Point, ToSec1Point},
+    CurveArithmetic, FieldBytes, NonZeroScalar, PrimeField,
 };
 use sys::*;
 use zeroize::Zeroizing;
@@ -631,6 +632,91 @@ pub mod gpu {
         check(unsafe { ecgpu_hash_to_scalar_batch(eng.0, C::ID, msgs.as_ptr(), msg_len, n, dst.as_ptr(), dst.len(), out.as_mut_ptr()) })?;
         Some(out)
     }
+
+    /// Batch form of `sm2::pke::EncryptingKey::encrypt_cipher_with_buf` (sm2/src/pke/encrypting.rs:166-230) under ONE public key:
+    /// `msgs` holds `n` messages of `msg_len` bytes (at least 1) each.  The nonces come from the caller's rng as in the reference's
+    /// loop (`NonZeroScalar::try_generate_from_rng`); an element the device answers with ok = 0 — its keystream was all zero —
+    /// gets another nonce and goes again, which is what the reference's `loop` does.  The ciphertexts are assembled in `mode`
+    /// (`04 || C1 || C3 || C2` for `Mode::C1C3C2`, `04 || C1 || C2 || C3` for `Mode::C1C2C3`), as `Cipher::to_vec(mode, false)`.
+    /// (x2, y2) never leaves the device.
+    pub fn sm2_pke_encrypt_batch<R: TryCryptoRng>(key: &sm2::PublicKey, mode: sm2::pke::Mode, rng: &mut R, msgs: &[u8], msg_len: usize, n: usize)
+                                                  -> Option<Vec<Vec<u8>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        assert!(msg_len > 0 && msgs.len() == n * msg_len);
+        let point = key.as_affine().to_sec1_point(false);
+        let pk_one = &point.as_bytes()[1..];
+        let mut out: Vec<Vec<u8>> = vec![Vec::new(); n];
+        let mut todo: Vec<usize> = (0..n).collect();
+        while !todo.is_empty() {
+            let m = todo.len();
+            let mut nonces = Zeroizing::new(Vec::with_capacity(32 * m));
+            let mut batch = Zeroizing::new(Vec::with_capacity(m * msg_len));
+            let mut pk = Vec::with_capacity(64 * m);
+            for &i in &todo {
+                let k = NonZeroScalar::<sm2::Sm2>::try_generate_from_rng(rng).ok()?;
+                nonces.extend_from_slice(&k.to_repr());
+                batch.extend_from_slice(&msgs[i * msg_len..(i + 1) * msg_len]);
+                pk.extend_from_slice(pk_one);
+            }
+            let (mut c1, mut c2, mut c3, mut ok) = (vec![0u8; 64 * m], vec![0u8; m * msg_len], vec![0u8; 32 * m], vec![0u8; m]);
+            check(unsafe {
+                ecgpu_sm2_pke_encrypt_batch(eng.0, pk.as_ptr(), nonces.as_ptr(), batch.as_ptr(), msg_len, m, c1.as_mut_ptr(), c2.as_mut_ptr(),
+                                            c3.as_mut_ptr(), ok.as_mut_ptr())
+            })?;
+            let mut again = Vec::new();
+            for (j, &i) in todo.iter().enumerate() {
+                if ok[j] == 0 {
+                    again.push(i);                        // t was all zero: the reference's loop draws another k
+                    continue;
+                }
+                let (p, e, h) = (&c1[64 * j..64 * j + 64], &c2[j * msg_len..(j + 1) * msg_len], &c3[32 * j..32 * j + 32]);
+                let mut ct = Vec::with_capacity(1 + 64 + 32 + msg_len);
+                ct.push(0x04);
+                ct.extend_from_slice(p);
+                match mode {
+                    sm2::pke::Mode::C1C3C2 => { ct.extend_from_slice(h); ct.extend_from_slice(e); }
+                    sm2::pke::Mode::C1C2C3 => { ct.extend_from_slice(e); ct.extend_from_slice(h); }
+                }
+                out[i] = ct;
+            }
+            todo = again;
+        }
+        Some(out)
+    }
+
+    /// Batch form of `sm2::pke::DecryptingKey::decrypt_cipher_with_buf` (sm2/src/pke/decrypting.rs:174-222) for ciphertexts of ONE
+    /// length under one secret key each: every ciphertext is split as `Cipher::from_slice(cipher, mode)` splits it (sm2/src/pke.rs:
+    /// 122-160; the uncompressed tag only — a compressed C1 goes through `ecgpu::gpu::batch_decompress` first); the point checks,
+    /// the KDF and the C3 comparison run on the device.  `None` per element where the reference returns `Err`.
+    pub fn sm2_pke_decrypt_batch(keys: &[NonZeroScalar<sm2::Sm2>], mode: sm2::pke::Mode, ciphers: &[&[u8]]) -> Option<Vec<Option<Zeroizing<Vec<u8>>>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = ciphers.len();
+        assert!(keys.len() == n);
+        if n == 0 {
+            return Some(Vec::new());
+        }
+        let total = ciphers[0].len();
+        assert!(total >= 1 + 64 + 32 && ciphers.iter().all(|c| c.len() == total && c[0] == 0x04));
+        let msg_len = total - (1 + 64 + 32);
+        let mut d = Zeroizing::new(Vec::with_capacity(32 * n));
+        let (mut c1, mut c2, mut c3) = (Vec::with_capacity(64 * n), Vec::with_capacity(n * msg_len), Vec::with_capacity(32 * n));
+        for (k, c) in keys.iter().zip(ciphers) {
+            d.extend_from_slice(&k.to_repr());
+            c1.extend_from_slice(&c[1..65]);
+            let rest = &c[65..];
+            let (e, h) = match mode {
+                sm2::pke::Mode::C1C3C2 => (&rest[32..], &rest[..32]),
+                sm2::pke::Mode::C1C2C3 => rest.split_at(msg_len),
+            };
+            c2.extend_from_slice(e);
+            c3.extend_from_slice(h);
+        }
+        let (mut out, mut ok) = (Zeroizing::new(vec![0u8; n * msg_len]), vec![0u8; n]);
+        check(unsafe {
+            ecgpu_sm2_pke_decrypt_batch(eng.0, d.as_ptr(), c1.as_ptr(), c2.as_ptr(), msg_len, c3.as_ptr(), n, out.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some((0..n).map(|i| if ok[i] != 0 { Some(Zeroizing::new(out[i * msg_len..(i + 1) * msg_len].to_vec())) } else { None }).collect())
+    }
 }
 
 // =====================================================================================================================
@@ -719,6 +805,17 @@ pub mod gpu {
 //     whose `sign_prehash` maps every prehash through `bits2field` and calls `ecgpu::gpu::batch_sign_prehash::<C>` with
 //     `C::NORMALIZE_S` (fallback: `PrehashSigner::sign_prehash` per key); `BatchSigner::sign(msgs, msg_len)` goes to
 //     `ecgpu::gpu::batch_sign`.  The signatures are byte-identical to the reference's (tests/golden/signing.json).
+//
+// (3b) sm2/src/pke/encrypting.rs and decrypting.rs gain the batch forms beside `EncryptingKey::encrypt_cipher_with_buf` and
+//     `DecryptingKey::decrypt_cipher_with_buf` (one element at a time in the reference):
+//
+//         #[cfg(feature = "gpu")]
+//         pub fn encrypt_batch<R: TryCryptoRng>(&self, rng: &mut R, msgs: &[u8], msg_len: usize, n: usize) -> Result<Vec<Vec<u8>>> {
+//             ecgpu::gpu::sm2_pke_encrypt_batch(&self.public_key, self.mode, rng, msgs, msg_len, n).ok_or(Error)
+//         }
+//
+//     and `ecgpu::gpu::sm2_pke_decrypt_batch(&keys, mode, &ciphers)` for a server that decrypts for many keys.  The nonce loop,
+//     the `Mode` byte order and the SEC1 tag stay on the Rust side; (x2, y2) stays on the device.
 //
 // (4) primeorder curves select their generator-multiplication backend through `PrimeCurveParams::Backend`
 //     (primeorder/src/lib.rs:62; p256/src/arithmetic/tables.rs:24-44).  `GpuBackend` below is such a backend: single calls

@@ -887,6 +887,29 @@ unsafe extern "C" {
         out_xy: *mut u8,
         out_inf: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_sm2_pke_encrypt_batch(
+        ctx: *mut EcgpuCtx,
+        pk_xy: *const u8,
+        k: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        n: usize,
+        out_c1_xy: *mut u8,
+        out_c2: *mut u8,
+        out_c3: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_sm2_pke_decrypt_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        c1_xy: *const u8,
+        c2: *const u8,
+        msg_len: usize,
+        c3: *const u8,
+        n: usize,
+        out_msgs: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_selftest_field(
         ctx: *mut EcgpuCtx,
         curve: c_int,

@@ -724,6 +724,43 @@ int ecgpu_hash_to_scalar_batch(ecgpu_ctx *ctx, int curve, const uint8_t *msgs, s
                                size_t dst_len, uint8_t *out_scalars);
 int ecgpu_map_to_curve_batch(ecgpu_ctx *ctx, int curve, const uint8_t *u, int per_point, size_t n, uint8_t *out_xy, uint8_t *out_inf);
 
+/* Batch SM2 public-key encryption and decryption (GB/T 32918.4) — `sm2::pke`.  Replaces, for a batch,
+ *   ecgpu_sm2_pke_encrypt_batch   `EncryptingKey::encrypt_cipher_with_buf` (sm2/src/pke/encrypting.rs:166-230) with the CALLER'S
+ *                                 nonce, the hazmat shape ecgpu_ecdsa_sign_batch has: C1 = k G, (x2, y2) = k P_B,
+ *                                 t = KDF(x2 || y2, msg_len), C2 = M ^ t, C3 = SM3(x2 || M || y2)
+ *   ecgpu_sm2_pke_decrypt_batch   the point checks of `Cipher::from_slice` (sm2/src/pke.rs:131-143) and
+ *                                 `DecryptingKey::decrypt_cipher_with_buf` (sm2/src/pke/decrypting.rs:174-222): (x2, y2) = d C1,
+ *                                 M' = C2 ^ KDF(x2 || y2, msg_len), ok = (SM3(x2 || M' || y2) == C3)
+ * with KDF block j (32 bytes) = SM3(x2 || y2 || I2OSP(j + 1, 4)) (sm2/src/pke.rs:349-381).  The reference's functions are generic
+ * but instantiated for Sm2 with Sm3 only: the calls take no curve argument.
+ * Wire format.  pk_xy, c1_xy: n*64 bytes, big-endian x || y; k, d: n*32 bytes, big-endian; msgs, c2, out_c2, out_msgs: n*msg_len
+ * bytes, ONE uniform msg_len per call (as ecgpu_ecdsa_sign_msg_batch); c3, out_c3: n*32 bytes.  The `Mode` byte order (C1C3C2 /
+ * C1C2C3), the SEC1 tag and the ASN.1 form stay with the caller, as DER stays outside the signing calls.
+ * encrypt: ok[i] = 1 iff 1 <= k < n, P_B has both coordinates below p and lies on the curve, and t is not all zero (where the
+ * reference's `loop` redraws k, the element gets ok = 0 here and the caller redraws).  An element with ok = 0 gets all-zero C1, C2
+ * and C3 records and its neighbours are untouched; no element fails the batch.  Step A3 of the reference (S = [h] P_B, reject the
+ * identity) multiplies by `Scalar::S`, the 2-adicity of n - 1, which is 1 for SM2's order, and the cofactor is 1 too: the step
+ * reduces to "P_B is not the identity", which the x || y wire format cannot express anyway.
+ * decrypt: ok[i] = 1 iff 1 <= d < n, C1 is on the curve with coordinates below p, and u == C3.  C1 and C3 come from an untrusted
+ * ciphertext: a bad one is a per-element verdict, never ECGPU_ERR_POINT for the call.  With ok = 0 the output record is zero:
+ * unauthenticated plaintext is not released.  One d per element (a server decrypting for many keys is one call; a caller with one
+ * key repeats it).  msg_len == 0 is legal: ok = (SM3(x2 || y2) == C3), and c2 / out_msgs may be NULL.
+ * ONE DEPARTURE from the reference: ecgpu_sm2_pke_encrypt_batch with msg_len == 0 returns ECGPU_ERR_ARG.  With an empty message the
+ * reference's loop never terminates (`any` over an empty range is false on every draw).
+ * Both: msg_len > 0xFFFFFFFF is ECGPU_ERR_ARG (the reference's i32 block counter cannot overflow below that); a NULL array with
+ * n > 0 or a NULL ctx is ECGPU_ERR_ARG; n == 0 succeeds.
+ * SECRECY: k, d, (x2, y2), t and the messages are secret.  Both multiplications are the uniform-schedule kernels of the `_ct`
+ * forms; in the kernels around them (k_pke_load, k_pke_seal, k_pke_open) no branch and no address depends on k, d, x2, y2, t, a
+ * message byte or the outcome of the C3 comparison (tools/ct_isa_check.py --unit pke); msg_len and n are public.  The public point
+ * (P_B, C1) is checked by a kernel of its own that may branch on it.  (x2, y2) never leaves the device.  The context's copies —
+ * the sanitised scalars, x2 || y2, the projective points, the staged k, d and messages — are zeroed behind the call like those of
+ * the `_ct` forms (and by ecgpu_wipe).
+ * These calls have host-pointer forms only; from 2^19 elements on they run the chunked pipeline (see the preamble). */
+int ecgpu_sm2_pke_encrypt_batch(ecgpu_ctx *ctx, const uint8_t *pk_xy, const uint8_t *k, const uint8_t *msgs, size_t msg_len,
+                                size_t n, uint8_t *out_c1_xy, uint8_t *out_c2, uint8_t *out_c3, uint8_t *ok);
+int ecgpu_sm2_pke_decrypt_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *c1_xy, const uint8_t *c2, size_t msg_len,
+                                const uint8_t *c3, size_t n, uint8_t *out_msgs, uint8_t *ok);
+
 /* Device-side known-answer tests of the arithmetic the kernels are built from — the same field / group code the CPU
  * host checks run (tests/hostcheck), here as gfx950 code, one lane per element; host buffers.
  * ecgpu_selftest_field: out[i] = op(a[i], b[i]) on canonical field elements (L bytes each; b may be NULL for unary ops).

@@ -11,6 +11,11 @@ retry loop whose trip count depends on the rejected candidates on purpose: repor
     python tools/ct_isa_check.py --unit h2c [--curve ...] [--kernels ...]
 the hash-to-curve kernels (csrc/ecgpu_h2c.h, translation unit ecgpu_inst_h2c.hip; k256, p256, p384): message bytes, the DST, the
 digests between the passes of the expander, u and the points are all loaded records; msg_len, count and n are kernel arguments.
+    python tools/ct_isa_check.py --unit pke --curve Sm2Params [--kernels ...]
+the SM2 public-key encryption kernels (csrc/ecgpu_pke.h, translation unit ecgpu_inst_sign.hip; sm2 only): k, d, the affine
+x2 || y2, the keystream, the message bytes and the C3 comparison are all loaded records or derived from them; msg_len and n are
+kernel arguments.  k_pke_load is the SCALAR half of the load step and passes as a whole; the public point (P_B, or the C1 of an
+untrusted ciphertext) is checked by k_pke_point, a kernel of its own that branches on the point on purpose and is not on the list.
 
 How: the translation unit is compiled to assembly (hipcc -S --offload-device-only; no GPU needed) and every selected kernel
 goes through a forward taint analysis over its control-flow graph (register-precise, iterated to a fixed point):
@@ -374,6 +379,7 @@ UNITS = {
     "ct": ("ecgpu_inst_ct.hip", "k_var_base_ct,k_fixed_base_ct,k_proj_sum_level"),
     "sign": ("ecgpu_inst_sign.hip", "k_rfc6979_first,k_schnorr_nonce,k_ecdsa_sign_finish,k_schnorr_sign_finish,k_sign_nonce_load"),
     "h2c": ("ecgpu_inst_h2c.hip", "k_h2c_expand,k_h2c_map"),
+    "pke": ("ecgpu_inst_sign.hip", "k_pke_load,k_pke_seal,k_pke_open"),
 }
 
 
@@ -406,7 +412,7 @@ def check(asm, wanted, verbose=False, seen_names=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="append")
-    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, or the hash-to-curve kernels")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, or the SM2 encryption kernels")
     ap.add_argument("--kernels", help="default: the data-independent kernels of the unit")
     ap.add_argument("--must-flag", default="", help="kernels of the unit that must be reported (comma-separated)")
     ap.add_argument("--asm", help="check an existing .s file instead of compiling")
