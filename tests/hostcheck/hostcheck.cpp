@@ -545,6 +545,36 @@ int msm(int c, size_t chunk, const uint8_t* scalars, const uint8_t* pxy, const u
     return 0;
 }
 
+// what k_msm_prepare writes per (term, half, window): MsmSplit::split, then MsmDigitStream in window order.  Scalar t of the n
+// given is term term_index + t of an MSM padded to npad terms (its second half: sub-term npad + term_index + t).
+// out[(t * SUB + h) * nwin + w] = bucket | neg << 16 | nonzero << 17; returns nwin.
+template <class C, bool GLV>
+int msm_digits(int c, uint32_t term_index, uint32_t npad, const uint8_t* scalars, size_t n, uint32_t* out) {
+    using S = MsmSplit<C, GLV>;
+    if (c < 4 || c > 16) return -1;
+    const int nwin = signed_window_count(S::KBITS, c);
+    for (size_t t = 0; t < n; t++) {
+        uint32_t k[C::N];
+        if (!load_scalar<C>(k, scalars + t * WireBytes<C>::value)) return -2;
+        uint32_t sub[S::SUB][S::KW];
+        bool neg[S::SUB];
+        S::split(k, sub, neg);
+        for (int h = 0; h < S::SUB; h++) {
+            MsmDigitStream<S::KW> ds;
+            ds.init(sub[h]);
+            for (int w = 0; w < nwin; w++) {
+                MsmDigit d = ds.next(w, c, nwin, (uint32_t)(h * npad + term_index + t), neg[h], S::KBITS);
+                out[(t * S::SUB + h) * nwin + w] = d.bucket | (d.neg << 16) | ((uint32_t)d.nonzero << 17);
+            }
+        }
+    }
+    return nwin;
+}
+template <class C>
+int msm_digits_plain(int c, uint32_t term_index, uint32_t npad, const uint8_t* scalars, size_t n, uint32_t* out) {
+    return msm_digits<C, false>(c, term_index, npad, scalars, n, out);
+}
+
 template <class C>
 int msm_plain(int c, size_t chunk, const uint8_t* scalars, const uint8_t* pxy, const uint8_t* pinf, size_t n, uint8_t* out_xy,
               uint8_t* out_inf) {
@@ -861,6 +891,11 @@ int hc_msm(int curve, int c, size_t chunk, int glv, const uint8_t* s, const uint
            uint8_t* oi) {
     if (glv) return curve == 0 ? msm<K256Params, true>(c, chunk, s, p, pi, n, o, oi) : -1;
     DISPATCH(curve, msm_plain, (c, chunk, s, p, pi, n, o, oi))
+}
+// the digits k_msm_prepare derives from n scalars (see msm_digits above); glv as for hc_msm
+int hc_msm_digits(int curve, int glv, int c, uint32_t term_index, uint32_t npad, const uint8_t* s, size_t n, uint32_t* out) {
+    if (glv) return curve == 0 ? msm_digits<K256Params, true>(c, term_index, npad, s, n, out) : -1;
+    DISPATCH(curve, msm_digits_plain, (c, term_index, npad, s, n, out))
 }
 int hc_ecdsa_verify(int curve, const uint8_t* z, const uint8_t* r, const uint8_t* s, const uint8_t* q, size_t n, int reject_high_s,
                     uint8_t* ok) {

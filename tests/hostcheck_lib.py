@@ -171,6 +171,20 @@ def msm(curve, c, scalars, pxy, pinf=None, chunk=32, glv=None):
     return res
 
 
+def msm_digits(curve, glv, c, term_index, npad, scalars):
+    """What k_msm_prepare derives from each scalar (MsmSplit::split, then MsmDigitStream): per scalar t, per half, per window
+    the tuple (bucket, neg, nonzero), with scalar t taken as term term_index + t of an MSM padded to npad terms."""
+    s = _a(scalars)
+    n = s.size // L[curve]
+    sub = 2 if glv else 1
+    out = np.zeros(max(n, 1) * sub * 140, np.uint32)                 # at most 543 / 4 + 1 = 136 windows
+    nwin = lib().hc_msm_digits(curve, int(bool(glv)), c, ctypes.c_uint32(term_index), ctypes.c_uint32(npad), _p(s), ctypes.c_size_t(n),
+                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    assert 0 < nwin <= 140, nwin
+    v = out[: n * sub * nwin].reshape(n, sub, nwin)
+    return [[[(int(x) & 0xFFFF, (int(x) >> 16) & 1, bool(int(x) >> 17)) for x in half] for half in term] for term in v]
+
+
 def ecdsa_verify(curve, z, r, s, q, reject_high_s=False):
     Z, R, S, Q = _a(z), _a(r), _a(s), _a(q)
     n = Z.size // L[curve]
