@@ -21,6 +21,15 @@
 
 #include "ecgpu_params.h"
 
+// The bounds-checking host build (-DECGPU_BOUNDS_CHECK, tests/hostcheck) traps where an interval stated in this file does not hold:
+// tools/modinv_model.py asserts the same ones on the Python restatement.  The device compile sees an empty statement.
+#if defined(ECGPU_BOUNDS_CHECK) && !defined(__HIP_DEVICE_COMPILE__)
+#define ECGPU_MODINV_CHECKED 1
+#define ECGPU_MODINV_CHECK(cond) do { if (!(cond)) __builtin_trap(); } while (0)
+#else
+#define ECGPU_MODINV_CHECK(cond) ((void)0)
+#endif
+
 namespace ecgpu {
 
 template <int NW>          // modulus size in 32-bit words: 6, 7, 8, 12 or 17
@@ -37,6 +46,51 @@ struct ModInv {
     struct Trans {
         int32_t u, v, q, r;
     };
+
+#if defined(ECGPU_MODINV_CHECKED)
+    // sign of a + k p (k small), exact
+    static int sign_of(const S30& a, int k, const S30& p) {
+        int64_t c = 0;
+        int32_t nz = 0;
+        for (int i = 0; i + 1 < NL; i++) {
+            const int64_t t = (int64_t)a.v[i] + (int64_t)k * p.v[i] + c;
+            c = t >> 30;
+            nz |= (int32_t)(t & M30);
+        }
+        const int64_t t = (int64_t)a.v[NL - 1] + (int64_t)k * p.v[NL - 1] + c;
+        return t < 0 ? -1 : (t > 0 || nz) ? 1 : 0;
+    }
+    static bool in_de_interval(const S30& a, const S30& p) { return sign_of(a, 2, p) > 0 && sign_of(a, -1, p) < 0; }      // (-2p, p)
+    static bool entry_ok(int32_t x) { return x >= -(1 << 30) && x <= (1 << 30); }
+    static bool trans_ok(const Trans& t) { return entry_ok(t.u) && entry_ok(t.v) && entry_ok(t.q) && entry_ok(t.r); }
+    // the end of an inversion: g = 0 and f = +-1 (f = +-p when the input was 0 mod p)
+    static bool end_ok(const S30& f, const S30& g, const S30& p) {
+        S30 one;
+        for (int i = 0; i < NL; i++) {
+            if (g.v[i] != 0) return false;
+            one.v[i] = i == 0 ? 1 : 0;
+        }
+        return sign_of(f, -1, one) == 0 || sign_of(f, 1, one) == 0 || sign_of(f, -1, p) == 0 || sign_of(f, 1, p) == 0;
+    }
+    // the result: limbs in [0, 2^30), value in [0, p)
+    static bool result_ok(const S30& d, const S30& p) {
+        for (int i = 0; i < NL; i++)
+            if (d.v[i] < 0 || d.v[i] > M30) return false;
+        return sign_of(d, -1, p) < 0;
+    }
+#endif
+#if !defined(__HIP_DEVICE_COMPILE__)
+    // acc + a b on the host; the bounds-checking build traps where the int64_t accumulator would overflow
+    static int64_t host_mad(int64_t acc, int32_t a, int32_t b) {
+#if defined(ECGPU_MODINV_CHECKED)
+        int64_t r;
+        if (__builtin_add_overflow(acc, (int64_t)a * b, &r)) __builtin_trap();
+        return r;
+#else
+        return acc + (int64_t)a * b;
+#endif
+    }
+#endif
 
     static ECGPU_HD S30 from_words(const uint32_t* w) {
         S30 r;
@@ -137,6 +191,7 @@ struct ModInv {
         t->v = (int32_t)(uint32_t)v;
         t->q = (int32_t)(uint32_t)q;
         t->r = (int32_t)(uint32_t)r;
+        ECGPU_MODINV_CHECK(trans_ok(*t));
         return zeta;
     }
 
@@ -152,7 +207,7 @@ struct ModInv {
         else asm("v_mad_i64_i32 %0, vcc, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(acc) : "vcc");
         return r;
 #else
-        return acc + (int64_t)a * b;
+        return host_mad(acc, a, b);
 #endif
     }
 
@@ -168,8 +223,8 @@ struct ModInv {
             : "+v"(cx), "+v"(cy), "=&s"(carry)
             : "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(b1), "v"(b2));
 #else
-        cx += (int64_t)a1 * b1 + (int64_t)a2 * b2;
-        cy += (int64_t)a3 * b1 + (int64_t)a4 * b2;
+        cx = host_mad(host_mad(cx, a1, b1), a2, b2);
+        cy = host_mad(host_mad(cy, a3, b1), a4, b2);
 #endif
     }
     // the same + the multiples of the modulus limb pl (wave-uniform: a scalar register): cx += pl mx, cy += pl my
@@ -186,8 +241,8 @@ struct ModInv {
             : "+v"(cx), "+v"(cy), "=&s"(carry)
             : "v"(a1), "v"(a2), "v"(a3), "v"(a4), "v"(b1), "v"(b2), "s"(pl), "v"(mx), "v"(my));
 #else
-        cx += (int64_t)a1 * b1 + (int64_t)a2 * b2 + (int64_t)pl * mx;
-        cy += (int64_t)a3 * b1 + (int64_t)a4 * b2 + (int64_t)pl * my;
+        cx = host_mad(host_mad(host_mad(cx, a1, b1), a2, b2), pl, mx);
+        cy = host_mad(host_mad(host_mad(cy, a3, b1), a4, b2), pl, my);
 #endif
     }
 
@@ -197,13 +252,17 @@ struct ModInv {
         const int32_t sd = d.v[NL - 1] >> 31, se = e.v[NL - 1] >> 31;
         int32_t md = (u & sd) + (v & se);
         int32_t me = (q & sd) + (r & se);
+        ECGPU_MODINV_CHECK((int64_t)(u & sd) + (v & se) == md && (int64_t)(q & sd) + (r & se) == me);
         int32_t di = d.v[0], ei = e.v[0];
         int64_t cd = smad(u, di, smad(v, ei, 0));
         int64_t ce = smad(q, di, smad(r, ei, 0));
+        ECGPU_MODINV_CHECK((int64_t)md - (int64_t)((pinv30 * (uint32_t)cd + (uint32_t)md) & (uint32_t)M30) >= INT32_MIN &&
+                           (int64_t)me - (int64_t)((pinv30 * (uint32_t)ce + (uint32_t)me) & (uint32_t)M30) >= INT32_MIN);      // md, me fit an int32_t
         md -= (int32_t)((pinv30 * (uint32_t)cd + (uint32_t)md) & (uint32_t)M30);
         me -= (int32_t)((pinv30 * (uint32_t)ce + (uint32_t)me) & (uint32_t)M30);
         cd = smad<true>(p.v[0], md, cd);
         ce = smad<true>(p.v[0], me, ce);
+        ECGPU_MODINV_CHECK(((uint32_t)cd & (uint32_t)M30) == 0 && ((uint32_t)ce & (uint32_t)M30) == 0);
         cd >>= 30;                                         // the low 30 bits are zero by construction
         ce >>= 30;
 #pragma unroll
@@ -216,8 +275,10 @@ struct ModInv {
             e.v[i - 1] = (int32_t)ce & M30;
             ce >>= 30;
         }
+        ECGPU_MODINV_CHECK(cd == (int32_t)cd && ce == (int32_t)ce);
         d.v[NL - 1] = (int32_t)cd;
         e.v[NL - 1] = (int32_t)ce;
+        ECGPU_MODINV_CHECK(in_de_interval(d, p) && in_de_interval(e, p));
     }
     // (f, g) <- t (f, g) / 2^30, exact
     static ECGPU_HD void update_fg(S30& f, S30& g, const Trans& t) {
@@ -225,6 +286,7 @@ struct ModInv {
         int32_t fi = f.v[0], gi = g.v[0];
         int64_t cf = smad(u, fi, smad(v, gi, 0));
         int64_t cg = smad(q, fi, smad(r, gi, 0));
+        ECGPU_MODINV_CHECK(((uint32_t)cf & (uint32_t)M30) == 0 && ((uint32_t)cg & (uint32_t)M30) == 0);
         cf >>= 30;
         cg >>= 30;
 #pragma unroll
@@ -237,10 +299,13 @@ struct ModInv {
             g.v[i - 1] = (int32_t)cg & M30;
             cg >>= 30;
         }
+        ECGPU_MODINV_CHECK(cf == (int32_t)cf && cg == (int32_t)cg);
         f.v[NL - 1] = (int32_t)cf;
         g.v[NL - 1] = (int32_t)cg;
     }
-    // d in (-2p, p), sign of f -> sign * d reduced to [0, p) with limbs in [0, 2^30)
+    // d in (-2p, p), sign of f -> sign * d reduced to [0, p) with limbs in [0, 2^30).  (A negative d only arrives from invert_var:
+    // `invert` always runs at least one batch on g = 0, and such a batch — u = 2^30, md = 2^30 for d < 0 — adds p to a negative d;
+    // tools/modinv_model.py, tests/test_modinv_vectors.py.)
     static ECGPU_HD void normalize(S30& d, int32_t fsign, const S30& p) {
         int32_t cond_add = d.v[NL - 1] >> 31;
         const int32_t cond_neg = fsign >> 31;
@@ -267,6 +332,7 @@ struct ModInv {
             }
             d.v[i] = x;
         }
+        ECGPU_MODINV_CHECK(result_ok(d, p));
     }
 
     // out = x^-1 mod p (0 for x = 0); x canonical (< p), p odd, all as NW little-endian words
@@ -287,6 +353,7 @@ struct ModInv {
             update_de(d, e, t, p, pinv30);
             update_fg(f, g, t);
         }
+        ECGPU_MODINV_CHECK(end_ok(f, g, p));
         normalize(d, f.v[NL - 1], p);
         to_words(out, d);
     }
@@ -347,6 +414,7 @@ struct ModInv {
         t->v = (int32_t)v;
         t->q = (int32_t)q;
         t->r = (int32_t)r;
+        ECGPU_MODINV_CHECK(trans_ok(*t));
         return eta;
     }
     static ECGPU_HD void invert_var(uint32_t* out, const uint32_t* x, const uint32_t* pw) {
@@ -374,6 +442,7 @@ struct ModInv {
             if (any == 0) break;
 #endif
         }
+        ECGPU_MODINV_CHECK(end_ok(f, g, p));
         normalize(d, f.v[NL - 1], p);
         to_words(out, d);
     }

@@ -155,7 +155,8 @@ __global__ void __launch_bounds__(BLOCK) k_selftest_field(int op, const uint8_t*
 // field, raw domain, and scalars mod n (ecgpu_selftest_raw.h; ecgpu_selftest_field sends every op >= 30 here): 30 - 39 the field
 // operations at the magnitude limits of the parameter set, on operands that enter through F::unpack — limbs as the caller wrote
 // them, values in [p, 2p) included, so NO canonical check — and 40 - 44 ScalarN<C> (a * b, 1 / a, reduce_wire, is_high, to_mont ->
-// from_mont), whose operands are below n or, for reduce_wire, any wire value.  A kernel of its own, so that the code object of
+// from_mont), whose operands are below n or, for reduce_wire, any wire value.  46, 47: F::inv and F::inv<true> in the raw domain (the
+// operand is the very integer the division steps receive).  A kernel of its own, so that the code object of
 // k_selftest_field stays what it was.  It contains the k256 assembly blocks: 128 VGPRs or more (ecgpu_field.h), which
 // __launch_bounds__(BLOCK) grants.
 template <class C>
@@ -171,7 +172,7 @@ __global__ void __launch_bounds__(BLOCK) k_selftest_field_raw(int op, const uint
 #pragma unroll
         for (int t = 0; t < N; t++) wb[t] = 0;
     }
-    const bool known = op >= 40 ? selftest_scalar<C>(op - 40, wa, wb, wr) : selftest_field_raw<C>(op, wa, wb, wr);
+    const bool known = op >= 40 && op < 45 ? selftest_scalar<C>(op - 40, wa, wb, wr) : selftest_field_raw<C>(op, wa, wb, wr);
     if (!known) {
 #pragma unroll
         for (int t = 0; t < N; t++) wr[t] = 0;

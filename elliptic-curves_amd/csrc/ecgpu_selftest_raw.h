@@ -21,7 +21,7 @@ ECGPU_HD auto selftest_times(const typename Field<C>::M1& x) {
     else return Field<C>::add(selftest_times<C, M - 1>(x), x);
 }
 
-// Operations 30 - 39 on the words wa, wb (N little-endian words each, any value below 2^(32 N) whose limbs fit: below 2p or
+// Operations 30 - 39, 46 and 47 on the words wa, wb (N little-endian words each, any value below 2^(32 N) whose limbs fit: below 2p or
 // 2^(8 WireBytes)); with MP = MAXPROD, MM = MAXMAG, A1 = min(MP, MM), B1 = MP / A1, A2 = 5 / 4 / 3 / 2 for MP >= 25 / 16 / 9 /
 // else, B2 = MP / A2, SQ = SQLIM (Ri = R^-1, or 1 for k256):
 //   30 mul(A1 x, B1 y)                       31 mul(A2 x, B2 y)              32 sqr(SQ x)             33 mul(x, y)
@@ -29,7 +29,12 @@ ECGPU_HD auto selftest_times(const typename Field<C>::M1& x) {
 //   36 mul2(A2 x, floor(B2 / 2) y, A2 y, ceil(B2 / 2) x)
 //   37 norm(sub(s x, s y)), s = 3 for k256 and 6 otherwise
 //   38 to_canonical(x)                       39 is_zero(x) as 0 / 1 in the first word
-// 30 - 37 come back through Field::pack (the internal-domain value in [0, p)).  False for an unknown operation.
+//   46 inv(x)                                47 inv<true>(x)  (the variable-time division steps)
+// 46 and 47 (45 stays unknown: the op-range tests pin it): F::inv packs its operand and inverts the words, so x < p is EXACTLY the
+// integer ModInv::invert receives, and x in [p, 2p), p itself included, reaches it through pack's reduction — ModInv::invert wants
+// x < p (invert(p) is 1, not 0: tools/modinv_model.py), and pack is what guarantees it.  The result is x^-1 mod p for k256 and
+// x^-1 R^2 mod p for the Montgomery sets (0 for x = 0 mod p).
+// 30 - 37, 46 and 47 come back through Field::pack (the internal-domain value in [0, p)).  False for an unknown operation.
 template <class C>
 ECGPU_HD bool selftest_field_raw(int op, const uint32_t* wa, const uint32_t* wb, uint32_t* wr) {
     using F = Field<C>;
@@ -56,6 +61,8 @@ ECGPU_HD bool selftest_field_raw(int op, const uint32_t* wa, const uint32_t* wb,
 #pragma unroll
         for (int t = 1; t < C::N; t++) wr[t] = 0;
         break;
+    case 46: F::pack(wr, F::inv(x)); break;
+    case 47: F::pack(wr, F::template inv<true>(x)); break;
     default: return false;
     }
     return true;

@@ -779,6 +779,9 @@ int ecgpu_sm2_pke_decrypt_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t 
  *   35 sqr_sub(SQ a, 6 b) of every parameter set, 36 mul2(A2 a, floor(B2 / 2) b, A2 b, ceil(B2 / 2) a), 37 3 a - 3 b (k256) or
  *   6 a - 6 b, 38 to_canonical(a), 39 is_zero(a) as 0 / 1.  40 - 44, scalars modulo the group order (a, b < n): 40 a * b,
  *   41 1 / a (0 for 0), 42 reduce_wire(a) for any a < 2^(8 L), 43 is_high(a) as 0 / 1, 44 a through to_mont and from_mont.
+ *   46, 47, the raw domain again (45 is unknown): 1 / a by the branch-free and by the variable-time division steps on a as
+ *   written, so that a < p is the very integer the division steps receive and a in [p, 2p) is reduced in front of them; the result is the
+ *   internal-domain value a^-1 mod p (k256) or a^-1 R^2 mod p (the Montgomery sets), 0 for a = 0 mod p.
  * ecgpu_selftest_point: out[i] = op(P[i], Q[i]); op 0 P + Q (complete), 1 the same mixed, 2 2P, 3 -P, 4 P - Q, 5 the same
  *   mixed, and the incomplete formulas inside their domain (P, Q finite, P != +-Q): 6 2P (Jacobian), 7 2P + Q (Jacobian
  *   doubling + mixed addition), 8 P + Q (XYZZ mixed), 9 P + Q (XYZZ affine + affine), 10 (k256; n a multiple of 64) 32 P of

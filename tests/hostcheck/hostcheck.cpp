@@ -61,8 +61,9 @@ typename Field<C>::M1 times21(const typename Field<C>::M1& y) {
     }
 }
 
-// ops 30 - 39: the raw-domain operations of ecgpu_selftest_raw.h (operands through F::unpack, no canonical check; what the
-// device runs as k_selftest_field_raw)
+// ops 30 - 39, 46 and 47: the raw-domain operations of ecgpu_selftest_raw.h (operands through F::unpack, no canonical check; what
+// the device runs as k_selftest_field_raw).  46 / 47: F::inv / F::inv<true> on the operand as written — the integer that
+// ModInv::invert receives (tests/modinv_vectors.py)
 template <class C>
 int field_raw_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
     uint32_t wa[C::N], wb[C::N], wr[C::N];
