@@ -2798,14 +2798,23 @@ int ecgpu_selftest_point(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p_xy,
                          const uint8_t* q_inf, size_t n, uint8_t* out_xy, uint8_t* out_inf) {
     HostCall h(ctx, __func__, curve);
     if (h.bad(n && (!p_xy || !out_xy || !out_inf))) return h.rc;
+    // ops 20 - 26 (the cross-lane code of the MSM's tail; bits 8.. of op carry a count of doublings): whole waves, whole workgroups
+    // for the tree, and a second operand for all but the lane-shared doubling of a single point
+    const int code = op & 0xFF;
+    const bool tail = code >= 20;
+    if (h.bad(tail && (n % (code == 25 ? 256 : 64) != 0 || (op >> 8) > 64 || (code != 26 && !q_xy)))) return h.rc;
     if (n == 0) return ECGPU_OK;
     return staged(ctx, n, {{p_xy, &ctx->in0, 2 * h.L}, {p_inf, &ctx->in2, 1}, {q_xy, &ctx->in1, 2 * h.L}, {q_inf, &ctx->in3, 1}},
                   {{out_xy, &ctx->out0, 2 * h.L}, {out_inf, &ctx->out1, 1}}, [&](auto in, auto o, size_t m) {
                       int rc = reset_status(ctx);
                       if (rc != ECGPU_OK) return rc;
                       rc = dispatch(curve, [&](auto c) {
-                          launch_selftest_point<decltype(c)>(ctx->stream, op, (const uint8_t*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2],
-                                                             (const uint8_t*)in[3], m, (uint8_t*)o[0], (uint8_t*)o[1], ctx->d_status);
+                          if (tail)
+                              launch_selftest_msm<decltype(c)>(ctx->stream, op, (const uint8_t*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2],
+                                                               (const uint8_t*)in[3], m, (uint8_t*)o[0], (uint8_t*)o[1], ctx->d_status);
+                          else
+                              launch_selftest_point<decltype(c)>(ctx->stream, op, (const uint8_t*)in[0], (const uint8_t*)in[1], (const uint8_t*)in[2],
+                                                                 (const uint8_t*)in[3], m, (uint8_t*)o[0], (uint8_t*)o[1], ctx->d_status);
                           return (int)ECGPU_OK;
                       });
                       return rc != ECGPU_OK ? rc : finish(ctx);

@@ -1,5 +1,6 @@
 // ecgpu_inst_msm.hip — instantiates the Pippenger pipeline for -DECGPU_CURVE=...
 #include "ecgpu_msm.h"
+#include "ecgpu_selftest_msm.h"
 
 namespace ecgpu {
 
@@ -17,5 +18,7 @@ template void launch_msm_parts<CurveT>(const MsmPlan& p, hipStream_t s, const ui
                                        hipEvent_t ev_accumulated);
 template void launch_msm_finish<CurveT>(const MsmPlan& p, hipStream_t s, const uint32_t* parts_all, int nranks, uint32_t* wins,
                                         uint32_t* out, uint8_t* out_xy, uint8_t* out_inf);
+template void launch_selftest_msm<CurveT>(hipStream_t s, int op, const uint8_t* pxy, const uint8_t* pinf, const uint8_t* qxy,
+                                          const uint8_t* qinf, size_t n, uint8_t* out_xy, uint8_t* out_inf, int* status);
 
 }  // namespace ecgpu

@@ -18,7 +18,9 @@
 //
 // Statement for statement the model tools/rows_field_model.py (register widths asserted at every step, adversarial magnitudes,
 // results against Python's integers).  On the device: ecgpu_selftest_field op 16 (products against Field::mul) and
-// ecgpu_selftest_point op 10 (a chain of doublings against Group::dbl), tests/test_gpu_selftest.py.
+// ecgpu_selftest_point op 10 (a chain of doublings against Group::dbl), tests/test_gpu_selftest.py; ops 20 - 22 of
+// ecgpu_selftest_point (mul, norm64 and enter / step / leave on raw limbs, compared with the model limb for limb),
+// tests/test_gpu_msm_tail.py.
 #pragma once
 
 #include "ecgpu_point.h"

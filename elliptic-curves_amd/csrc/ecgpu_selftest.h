@@ -186,7 +186,8 @@ __global__ void __launch_bounds__(BLOCK) k_selftest_field_raw(int op, const uint
 // sees the identity otherwise): 6 2P by the Jacobian doubling, 7 P + Q by the Jacobian mixed addition, 8 P + Q by the
 // XYZZ mixed addition, 9 P + Q by the XYZZ affine + affine addition; 10 (k256; n a multiple of 64) 32 P of the WAVE'S FIRST point in
 // every lane, by five row-parallel complete doublings (ecgpu_rows.h RowsDblK256: what k_msm_combine's Horner chain runs on).
-// Output: affine + identity flag (one inversion per lane).
+// Output: affine + identity flag (one inversion per lane).  Ops 20 - 26 (the row field on raw limbs, the quad addition, the quad tree,
+// the lane-shared doubling: what the MSM runs behind its buckets) are k_selftest_msm, ecgpu_selftest_msm.h, in the msm group.
 template <class C>
 __global__ void __launch_bounds__(BLOCK) k_selftest_point(int op, const uint8_t* __restrict__ pxy, const uint8_t* __restrict__ pinf,
                                                           const uint8_t* __restrict__ qxy, const uint8_t* __restrict__ qinf, size_t n,

@@ -786,6 +786,16 @@ int ecgpu_sm2_pke_decrypt_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t 
  *   mixed, and the incomplete formulas inside their domain (P, Q finite, P != +-Q): 6 2P (Jacobian), 7 2P + Q (Jacobian
  *   doubling + mixed addition), 8 P + Q (XYZZ mixed), 9 P + Q (XYZZ affine + affine), 10 (k256; n a multiple of 64) 32 P of
  *   the wave's FIRST point in every lane, by five row-parallel complete doublings.
+ *   Ops 20 - 26, op = code | steps << 8 (steps <= 64): the cross-lane code behind the MSM's buckets, a kernel of its own
+ *   (csrc/ecgpu_selftest_msm.h); q_xy is required except for 26, n is a multiple of 64 (of 256 for 25), else ECGPU_ERR_ARG.
+ *   k256 on RAW records (a 64-byte record is sixteen little-endian 32-bit words, words 0 - 8 the nine 29-bit-radix limbs as they
+ *   are, nothing checked; the nine result limbs come back the same way, out_inf = 0): 20 the row-parallel multiplication, row r of a
+ *   wave on the p / q records of the wave's lane r, the product of row (i mod 4) in lane i; 21 its norm64 on the per-position
+ *   64-bit values p word | q word << 32, laid out the same way; 22 the row doubling chain: X, Y, Z = the p records of the wave's
+ *   lanes 0, 1, 2, `steps` doublings, coordinate (i mod 3) in lane i.  k256 on points: 23 the complete addition on the lanes of a
+ *   quad, P + Q of each quad's first lane in all four lanes; 24 the same on Group::add(P, Q) and Group::dbl(Q): P + 3 Q; 25 the
+ *   workgroup-wide tree sum of P over 256 lanes in the workgroup's first record (the identity in the others).  The a = -3 sets:
+ *   26 2^steps (P + Q) (P alone without q_xy) of the wave's first lane in every lane, by the Jacobian doubling shared by three lanes.
  * ECGPU_ERR_POINT: an input >= p (field ops 0 - 21) / off the curve; ECGPU_ERR_SCALAR_RANGE: unknown op. */
 int ecgpu_selftest_field(ecgpu_ctx *ctx, int curve, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
 int ecgpu_selftest_point(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p_xy, const uint8_t *p_inf, const uint8_t *q_xy,

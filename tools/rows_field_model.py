@@ -51,8 +51,9 @@ F1P = [F1 if 1 <= p <= 10 else 0 for p in range(NPOS)]    # multiplier of the li
 LOW9 = [1 if p <= 8 else 0 for p in range(NPOS)]
 
 
-def mul_rows(a, b, stats=None):
-    """a, b: rows with limbs at positions 0..8 (lazy: limb magnitudes ma, mb with ma mb <= 7), zeros above -> the product, limbs < LB"""
+def mul_rows(a, b, stats=None, events=None):
+    """a, b: rows with limbs at positions 0..8 (lazy: limb magnitudes ma, mb with ma mb <= 7), zeros above -> the product, limbs < LB.
+    events: a dict that takes what this product made happen (tests/msm_tail_vectors.py: the coverage of its vector families)"""
     assert all(x == 0 for x in a[9:]) and all(x == 0 for x in b[9:])
     # --- 16 product columns: c_p = sum_i a_i b_(p - i); a_i arrives through the LDS crossbar (a broadcast inside the row), b shifted
     # by i positions is one DPP move
@@ -79,10 +80,14 @@ def mul_rows(a, b, stats=None):
     r = [chk(c1[p] * LOW9[p] + F0P[p] * ha[p] + F1P[p] * hb[p], 64, "stage 2") for p in range(NPOS)]
     if stats is not None:
         stats["stage2"] = max(stats.get("stage2", 0), max(r))
+    if events is not None:
+        events.update(th=th, tm=tm, h0=h[0], h15=h[15], stage2=max(r), fold2=[F0P[p] * ha[p] + F1P[p] * hb[p] for p in range(11)])
     # --- stage 3: carry pass (two pieces: the values are < 2^46)
     l = [x & M for x in r]
     m = [chk(x >> B, 32, "stage 3 carry") for x in r]
     r1 = [chk(l[p] + shr(m, 1)[p], 32, "stage 3") for p in range(NPOS)]         # positions 0..11
+    if events is not None:
+        events.update(carry3=max(m), fold4=[r1[9], r1[10]])
     # --- stage 4: positions 9, 10 (and 11: zero) folded down once more
     ga, gb = shl(r1, 9), shl(r1, 8)
     r2 = [chk(r1[p] * LOW9[p] + F0P[p] * ga[p] + F1P[p] * gb[p], 64, "stage 4") for p in range(NPOS)]
@@ -95,6 +100,8 @@ def mul_rows(a, b, stats=None):
     assert all(x < LB for x in out[:9]), [hex(x) for x in out]
     if stats is not None:
         stats["out"] = max(stats.get("out", 0), max(out))
+    if events is not None:
+        events.update(carry5=m[:3], out=out[:9])
     return out
 
 
