@@ -585,11 +585,16 @@ int msm_plain(int c, size_t chunk, const uint8_t* scalars, const uint8_t* pxy, c
 // ---- the verification / decompression kernels' per-element logic (ecgpu_verify.h) around the CPU mirrors of the
 // fixed-base and variable-base kernels: k_ecdsa_prepare -> k_fixed_base + k_var_base (which adds its product to the fixed-base one) -> k_normalize ->
 // k_ecdsa_finish, element by element
+// The device's k_fixed_base / k_var_base flag a scalar outside [0, n) (`load_scalar`) and the whole call fails with
+// ECGPU_ERR_SCALAR_RANGE, so the prepare code has to hand over reduced scalars whatever the element is; the mirrors below would
+// multiply by an unreduced scalar without complaint.  Counted here, read and cleared by hc_bad_scalars().
+static int g_bad_scalars = 0;
 template <class C>
 bool sum_affine_x(const BaseTable<C>& table, const uint32_t* a, const uint32_t* b, const uint32_t* cx, const uint32_t* cy,
                   uint32_t* x, uint32_t* y) {
     using F = Field<C>;
     using G = Group<C>;
+    if (mp_geq<C::N>(a, C::ORDER) || mp_geq<C::N>(b, C::ORDER)) g_bad_scalars++;
     Affine<C> q;
     q.x = F::from_canonical(cx).e;
     q.y = F::from_canonical(cy).e;
@@ -903,6 +908,8 @@ int hc_ecdsa_verify(int curve, const uint8_t* z, const uint8_t* r, const uint8_t
     if (curve == 3 || curve == 11) return -1;                    // sm2 / bign signatures are not ECDSA
     DISPATCH(curve, ecdsa_verify, (z, r, s, q, n, reject_high_s, ok))
 }
+// prepared scalars at or above n met by the verification / recovery mirrors since the last call (then cleared)
+int hc_bad_scalars() { const int v = g_bad_scalars; g_bad_scalars = 0; return v; }
 int hc_ecdsa_hash_msg(int curve, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* z_out) {
     DISPATCH(curve, ecdsa_hash_msg, (msgs, msg_len, n, z_out))
 }

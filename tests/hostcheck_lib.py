@@ -185,12 +185,20 @@ def msm_digits(curve, glv, c, term_index, npad, scalars):
     return [[[(int(x) & 0xFFFF, (int(x) >> 16) & 1, bool(int(x) >> 17)) for x in half] for half in term] for term in v]
 
 
+def _scalars_reduced():
+    """what the device's arithmetic kernels require of the prepare code: every scalar handed over below n (their `load_scalar` fails
+    the whole call otherwise)"""
+    bad = lib().hc_bad_scalars()
+    assert bad == 0, "%d prepared scalars were not reduced: the device call would fail with ECGPU_ERR_SCALAR_RANGE" % bad
+
+
 def ecdsa_verify(curve, z, r, s, q, reject_high_s=False):
     Z, R, S, Q = _a(z), _a(r), _a(s), _a(q)
     n = Z.size // L[curve]
     ok = np.zeros(n, np.uint8)
     rc = lib().hc_ecdsa_verify(curve, _p(Z), _p(R), _p(S), _p(Q), ctypes.c_size_t(n), int(bool(reject_high_s)), _p(ok))
     assert rc == 0, rc
+    _scalars_reduced()
     return ok
 
 
@@ -199,6 +207,7 @@ def sm2dsa_verify(e, r, s, q):
     n = E.size // 32
     ok = np.zeros(n, np.uint8)
     assert lib().hc_sm2dsa_verify(_p(E), _p(R), _p(S), _p(Q), ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -207,6 +216,7 @@ def schnorr_verify(e, r, s, p_xy):
     n = E.size // 32
     ok = np.zeros(n, np.uint8)
     assert lib().hc_schnorr_verify(0, _p(E), ctypes.c_size_t(0), _p(R), _p(S), _p(P), ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -216,6 +226,7 @@ def schnorr_verify_raw(pk_x, msgs, msg_len, sigs):
     n = PK.size // 32
     ok = np.zeros(n, np.uint8)
     assert lib().hc_schnorr_verify(1, _p(M), ctypes.c_size_t(msg_len), _p(SG), None, _p(PK), ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -240,6 +251,7 @@ def bign_verify(h, sigs, q):
     n = H.size // 32
     ok = np.zeros(n, np.uint8)
     assert lib().hc_bign_verify(_p(H), _p(SG), _p(Q), ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -249,6 +261,7 @@ def bign_verify_msg(q, msgs, msg_len, sigs):
     n = Q.size // 64
     ok = np.zeros(n, np.uint8)
     assert lib().hc_bign_verify_msg(_p(Q), _p(M), ctypes.c_size_t(msg_len), _p(SG), ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -267,6 +280,7 @@ def sm2dsa_verify_msg(distid, q, msgs, msg_len, sigs):
     ok = np.zeros(n, np.uint8)
     assert lib().hc_sm2dsa_verify_msg(_p(D), ctypes.c_size_t(len(distid)), _p(Q), _p(M), ctypes.c_size_t(msg_len), _p(SG),
                                       ctypes.c_size_t(n), _p(ok)) == 0
+    _scalars_reduced()
     return ok
 
 
@@ -277,6 +291,7 @@ def ecdsa_recover(curve, z, r, s, recid, reject_high_s=False):
     ok = np.zeros(n, np.uint8)
     rc = lib().hc_ecdsa_recover(curve, _p(Z), _p(R), _p(S), _p(I), ctypes.c_size_t(n), int(bool(reject_high_s)), _p(out), _p(ok))
     assert rc == 0, rc
+    _scalars_reduced()
     return out, ok
 
 
