@@ -23,67 +23,32 @@ namespace ecgpu {
 
 // ---- inverses modulo the group order for a whole batch: Montgomery's trick, one division-step inversion per LANE instead of one per
 // signature.  `Scalar::invert` (k256/src/arithmetic/scalar.rs:139-143; primefield/src/monty.rs:373-375) is what verification
-// (s^-1) and recovery (r^-1) call once per signature: 21.5 k dependent instructions each, 90 % of k_ecdsa_prepare.  Lane t owns
-// elements t, t + T, t + 2T, ... (a wave touches consecutive records, like k_normalize): running products in the Montgomery domain
-// (one multiplication per product), the prefix products parked in `prefix` (N words per element), one inversion of the lane's
-// product, a backward pass that peels the inverses off.  An element outside [1, n - 1] is left out of the product and gets 0 —
-// the prepare kernels fail it on their range check and never use its inverse.
+// (s^-1) and recovery (r^-1) call once per signature: 21.5 k dependent instructions each, 90 % of k_ecdsa_prepare.  The lanes are
+// those of k_normalize and the lane body is scalar_batch_inv_lane (ecgpu_batchinv.h); `prefix`: N words per element.
+template <class C>
+struct ScalarIoHbm {
+    static constexpr int N = C::N, WB = WireBytes<C>::value;
+    const uint8_t* in;
+    uint32_t* prefix;
+    uint8_t* out;
+    __device__ void load(size_t j, uint32_t* a) const { load_wire<C>(a, in + j * WB); }
+    __device__ void put(size_t j, const uint32_t* w) const { store_wire<C>(out + j * WB, w); }
+    __device__ void put_prefix(size_t j, const uint32_t* w) const {
+#pragma unroll
+        for (int i = 0; i < N; i++) prefix[j * N + i] = w[i];
+    }
+    __device__ void get_prefix(size_t j, uint32_t* w) const {
+#pragma unroll
+        for (int i = 0; i < N; i++) w[i] = prefix[j * N + i];
+    }
+};
 template <class C>
 __global__ void __launch_bounds__(BLOCK)
 k_scalar_batch_inv(const uint8_t* __restrict__ in, size_t n, size_t nthreads, uint32_t* __restrict__ prefix, uint8_t* __restrict__ out) {
-    using S = ScalarN<C>;
-    constexpr int N = C::N, WB = WireBytes<C>::value;
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= nthreads || t >= n) return;
-    uint32_t acc[N], one_m[N];
-    {
-        uint32_t one[N];
-#pragma unroll
-        for (int i = 0; i < N; i++) one[i] = i == 0 ? 1u : 0u;
-        S::to_mont(one_m, one);                                    // R mod n
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) acc[i] = one_m[i];
-    for (size_t j = t; j < n; j += nthreads) {
-        uint32_t a[N], am[N];
-        load_wire<C>(a, in + j * WB);
-        const bool ok = !S::is_zero(a) && S::in_range(a);
-        uint32_t* pj = prefix + j * N;
-#pragma unroll
-        for (int i = 0; i < N; i++) pj[i] = acc[i];                // the product of the lane's earlier elements (Montgomery form)
-        if (ok) {
-            S::to_mont(am, a);
-            S::mont_mul(acc, acc, am);
-        }
-    }
-    uint32_t inv[N];
-    {
-        // acc = P R as an integer; x = acc^-1 = P^-1 R^-1; x R2 / R = P^-1; P^-1 R2 / R = P^-1 R: the Montgomery form of P^-1
-        uint32_t x[N];
-        S::inv(x, acc);
-        S::to_mont(x, x);
-        S::to_mont(inv, x);
-    }
-    const size_t last = t + ((n - 1 - t) / nthreads) * nthreads;
-    for (size_t j = last;; j -= nthreads) {
-        uint32_t a[N], am[N], w[N];
-        load_wire<C>(a, in + j * WB);
-        const bool ok = !S::is_zero(a) && S::in_range(a);
-#pragma unroll
-        for (int i = 0; i < N; i++) w[i] = 0u;
-        if (ok) {
-            uint32_t pre[N], wm[N];
-            const uint32_t* pj = prefix + j * N;
-#pragma unroll
-            for (int i = 0; i < N; i++) pre[i] = pj[i];
-            S::mont_mul(wm, inv, pre);                             // (a_0 .. a_j)^-1 (a_0 .. a_(j-1)) = a_j^-1
-            S::to_mont(am, a);
-            S::mont_mul(inv, inv, am);                             // (a_0 .. a_(j-1))^-1
-            S::from_mont(w, wm);
-        }
-        store_wire<C>(out + j * WB, w);
-        if (j < nthreads) break;
-    }
+    if (t >= nthreads) return;
+    ScalarIoHbm<C> io{in, prefix, out};
+    scalar_batch_inv_lane<C>(t, n, nthreads, io);
 }
 
 // prepare: range checks, public-key validation, u1 / u2 as wire-format scalars for the scalar-mul kernels.

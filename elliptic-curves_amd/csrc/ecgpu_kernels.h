@@ -360,102 +360,94 @@ __global__ void __launch_bounds__(BLOCK) k_table_entries(const uint32_t* bases, 
 // ---- normalisation: (X:Y:Z) -> (X/Z, Y/Z) with Montgomery's trick --------------------------------
 // `BatchNormalize::batch_normalize` (k256 projective.rs:367-391 + field.rs:244-265; primeorder
 // projective.rs:452-478).  Lane t owns points t, t+T, t+2T, ... so that a wave always touches
-// consecutive records; one field inversion per lane amortised over its K = n/T points.
-// MODE NORM_WIRE      : big-endian canonical x||y records + identity flags (wire format)
-// MODE NORM_PACKED    : [n][2] packed elements (table entries; identities not expected)
-// MODE NORM_COMPRESSED: SEC1 compressed form split in two arrays: x (L bytes, to out_xy) and the tag byte 0x02 / 0x03
-//                       (y even / odd), 0x00 for the identity (to out_inf) — `ToSec1Point::to_sec1_point(true)`,
-//                       primeorder/src/affine.rs:387-401
-enum : int { NORM_WIRE = 0, NORM_PACKED = 1, NORM_COMPRESSED = 2 };
+// consecutive records; one field inversion per lane amortised over its K = n/T points.  What happens to a record — its class, the
+// prefix entry, zinv, the two multiplications, the output forms NORM_* — is NormRec (ecgpu_batchinv.h), which the CPU twin runs
+// too; here are the loads and stores, and the kernel's own walk over the lane's records.
 // SOA: `proj` and `prefix` are quad-major (store_proj_soa; what k_fixed_base<C, true> leaves) instead of record-major.
+template <class C, int MODE, bool SOA>
+struct NormIoHbm {
+    static constexpr int N = C::N, WB = WireBytes<C>::value, NS = Field<C>::NS;
+    const uint32_t* proj;
+    uint32_t* prefix;
+    size_t n;
+    uint8_t* out_xy;          // NORM_COMPRESSED: x alone
+    uint8_t* out_inf;         // NORM_COMPRESSED: the tags
+    uint32_t* out_packed;
+    __device__ Fe<C::NL> load_z(size_t j) const {
+        if constexpr (SOA) return load_raw_soa<C>(proj, n, j, 2);
+        else return load_raw<C>(proj + j * (3 * NS) + 2 * NS);
+    }
+    __device__ Proj<C> load_point(size_t j) const {
+        if constexpr (SOA) return load_proj_soa<C>(proj, n, j);
+        else return load_proj<C>(proj, j);
+    }
+    __device__ void put_prefix(size_t j, const uint32_t* w) const {
+        if constexpr (SOA) store_quads_soa<NS / 4>(prefix, n, j, 0, w);
+        else store_words_vec<NS>(prefix + j * NS, w);
+    }
+    __device__ void get_prefix(size_t j, uint32_t* w) const {
+        if constexpr (SOA) load_quads_soa<NS / 4>(w, prefix, n, j, 0);
+        else load_words_vec<NS>(w, prefix + j * NS);
+    }
+    __device__ void put_x(size_t j, const uint32_t* w) const {
+        if constexpr (MODE == NORM_PACKED) store_words_vec<N>(out_packed + j * (2 * N), w);
+        else store_wire<C>(out_xy + j * (MODE == NORM_WIRE ? 2 * WB : WB), w);
+    }
+    __device__ void put_y(size_t j, const uint32_t* w) const {
+        if constexpr (MODE == NORM_PACKED) store_words_vec<N>(out_packed + j * (2 * N) + N, w);
+        else store_wire<C>(out_xy + j * (2 * WB) + WB, w);
+    }
+    __device__ void put_flag(size_t j, uint8_t v) const {
+        if (MODE == NORM_COMPRESSED || out_inf) out_inf[j] = v;
+    }
+};
 template <class C, int MODE, bool SOA = false>
 __global__ void __launch_bounds__(BLOCK) k_normalize(const uint32_t* proj, uint32_t* prefix, size_t n, size_t nthreads,
                                                      uint8_t* out_xy, uint8_t* out_inf, uint32_t* out_packed) {
-    using F = Field<C>;
-    using G = Group<C>;
-    constexpr int N = C::N, NS = F::NS, WB = WireBytes<C>::value;
-    (void)N;
+    using Io = NormIoHbm<C, MODE, SOA>;
+    using Lane = FieldLane<NormRec<C, MODE, Io>>;
+    using El = typename Lane::El;
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= nthreads) return;
+    Io io{proj, prefix, n, out_xy, out_inf, out_packed};
+    Lane lane{{io}};
     // Both passes are software-pipelined by hand: the loads of the lane's NEXT point are issued before the multiplications of
     // the current one.  With one wave per SIMD (the launch is sized that way: one inversion per lane) nothing else hides a
     // load's ~2 us, and the loop-carried product keeps the compiler from hoisting the loads itself.
-    const auto load_z = [&](size_t j) -> Fe<C::NL> {
-        if constexpr (SOA) return load_raw_soa<C>(proj, n, j, 2);
-        else return load_raw<C>(proj + j * (3 * NS) + 2 * NS);
-    };
-    const auto load_point = [&](size_t j) -> Proj<C> {
-        if constexpr (SOA) return load_proj_soa<C>(proj, n, j);
-        else return load_proj<C>(proj, j);
-    };
-    const auto load_prefix = [&](uint32_t* w, size_t j) {
-        if constexpr (SOA) load_quads_soa<NS / 4>(w, prefix, n, j, 0);
-        else load_words_vec<NS>(w, prefix + j * NS);
-    };
-    typename F::M1 acc = F::one();
-    Fe<C::NL> z_next = load_z(t < n ? t : 0);
+    El acc = lane.one(), f;
+    typename Lane::Fwd z_next;
+    lane.load_fwd(t < n ? t : 0, z_next);
     for (size_t j = t; j < n; j += nthreads) {
-        const Fe<C::NL> z = z_next;
-        if (j + nthreads < n) z_next = load_z(j + nthreads);
-        const bool ident = F::is_zero(G::m(z));
-        {   // running product before this point, and whether the point is the identity, in the spare word
-            static_assert(NS > C::NL, "raw form has no spare word");
-            uint32_t w[NS];
-#pragma unroll
-            for (int i = 0; i < NS; i++) w[i] = i < C::NL ? acc.e.v[i] : 0u;
-            w[NS - 1] = ident ? 1u : 0u;
-            if constexpr (SOA) store_quads_soa<NS / 4>(prefix, n, j, 0, w);
-            else store_words_vec<NS>(prefix + j * NS, w);
-        }
-        if (!ident) acc = F::mul(acc, G::m(z));
+        const typename Lane::Fwd z = z_next;
+        if (j + nthreads < n) lane.load_fwd(j + nthreads, z_next);
+        const uint32_t cls = lane.classify(j, z, f);
+        lane.put_prefix(j, acc, cls);               // running product before this point, and its class in the spare word
+        if (cls == 0) acc = lane.mul(acc, f);
     }
-    typename F::M1 inv = F::inv(acc);
+    El inv = lane.inv(acc);
     if (n <= t) return;
     size_t last = t + ((n - 1 - t) / nthreads) * nthreads;
-    Proj<C> p_next = load_point(last);
-    uint32_t pw_next[NS];
-    load_prefix(pw_next, last);
+    // (the next record in variables of its own, not in a Back: p256 needs six registers more otherwise, and loses a wave per SIMD)
+    Proj<C> p_next = io.load_point(last);
+    uint32_t pw_next[Lane::NS];
+    io.get_prefix(last, pw_next);
     for (size_t j = last;; j -= nthreads) {
-        const Proj<C> p = p_next;
-        uint32_t pw[NS];
+        typename Lane::Back r;
+        r.p = p_next;
 #pragma unroll
-        for (int i = 0; i < NS; i++) pw[i] = pw_next[i];
+        for (int i = 0; i < Lane::NS; i++) r.pw[i] = pw_next[i];
         if (j >= nthreads) {
-            p_next = load_point(j - nthreads);
-            load_prefix(pw_next, j - nthreads);
+            p_next = io.load_point(j - nthreads);
+            io.get_prefix(j - nthreads, pw_next);
         }
-        if (pw[NS - 1]) {
-            if constexpr (MODE == NORM_WIRE) {
-                zero_wire<C>(out_xy + j * (2 * WB), 2);
-                if (out_inf) out_inf[j] = 1;
-            } else if constexpr (MODE == NORM_COMPRESSED) {
-                zero_wire<C>(out_xy + j * WB, 1);
-                out_inf[j] = 0;
-            }
+        // (emit inside each branch, its class a literal: behind the merged branch the p192 / p224 / p256 instantiations need more
+        // than 128 registers and lose a wave per SIMD)
+        if (lane.classify(j, r, f) == 0) {
+            const El zinv = lane.mul(lane.prefix(j, r), inv);
+            inv = lane.mul(inv, f);
+            lane.emit(j, r, 0u, zinv);
         } else {
-            Fe<C::NL> pre_e;
-#pragma unroll
-            for (int i = 0; i < C::NL; i++) pre_e.v[i] = pw[i];
-            typename F::M1 pre = G::m(pre_e);
-            typename F::M1 zinv = F::mul(pre, inv);
-            inv = F::mul(inv, G::m(p.z));
-            typename F::M1 x = F::mul(G::m(p.x), zinv), y = F::mul(G::m(p.y), zinv);
-            if constexpr (MODE == NORM_PACKED) {
-                store_packed_affine<C>(out_packed + j * (2 * N), x.e, y.e);
-            } else if constexpr (MODE == NORM_COMPRESSED) {
-                uint32_t w[N];
-                F::to_canonical(w, x);
-                store_wire<C>(out_xy + j * WB, w);
-                F::to_canonical(w, y);
-                out_inf[j] = (uint8_t)(2u + (w[0] & 1u));
-            } else {
-                uint32_t w[N];
-                F::to_canonical(w, x);
-                store_wire<C>(out_xy + j * (2 * WB), w);
-                F::to_canonical(w, y);
-                store_wire<C>(out_xy + j * (2 * WB) + WB, w);
-                if (out_inf) out_inf[j] = 0;
-            }
+            lane.emit(j, r, 1u, inv);
         }
         if (j < nthreads) break;
     }
@@ -465,8 +457,8 @@ __global__ void __launch_bounds__(BLOCK) k_normalize(const uint32_t* proj, uint3
 // (ecgpu_msm_xyz, ecgpu_batch_mul_xyz, ecgpu_batch_mul_base_and_mul_add_xyz, ecgpu_msm_parts_xyz_dev: the affine pipelines run
 // unchanged behind it).  Lanes and the inversion per lane as in k_normalize, but the records are read from the caller's wire
 // array itself — Z in the product pass, X || Y || Z and the prefix in the back pass — and no projective copy is made: 290 bytes
-// of traffic per k256 record against ~590 for k_load_proj + k_normalize.  The lane body, its verdicts and its reference
-// citations are in ecgpu_xyz.h.
+// of traffic per k256 record against ~590 for k_load_proj + k_normalize.  The lane body (a policy of batch_inv_lane,
+// ecgpu_batchinv.h), its verdicts and its reference citations are in ecgpu_xyz.h.
 template <class C>
 struct XyzIoHbm {
     static constexpr int WB = WireBytes<C>::value, NS = Field<C>::NS;

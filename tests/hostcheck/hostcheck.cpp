@@ -1,8 +1,8 @@
 // hostcheck.cpp — TEST INFRASTRUCTURE.  Compiles the exact __host__ __device__ arithmetic the gfx950
 // kernels use (csrc/ecgpu_field.h, ecgpu_point.h, ecgpu_recode.h) with g++ so that it can be checked
 // against the oracle on a machine without a GPU.  The driver loops below mirror the kernels' control
-// flow (k_fixed_base, k_var_base, k_normalize, the Pippenger pipeline) on one CPU thread.  Nothing here
-// is linked into libecgpu.so.
+// flow (k_fixed_base, k_var_base, the Pippenger pipeline) on one CPU thread; k_normalize and k_scalar_batch_inv run their own
+// lane bodies (batchinv_host.h).  Nothing here is linked into libecgpu.so.
 #include <cstring>
 #include <array>
 #include <vector>
@@ -20,6 +20,7 @@
 #include "../../elliptic-curves_amd/csrc/ecgpu_belt.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_verify.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_selftest_raw.h"
+#include "batchinv_host.h"
 
 using namespace ecgpu;
 
@@ -257,40 +258,6 @@ Proj<C> var_base_one(const Affine<C>& a, const uint32_t* k) {
     return var_base_mul<C>(a, k, Group<C>::curve_b(), tab);
 }
 
-// k_normalize<.., false> with `nthreads` strided lanes
-template <class C>
-void normalize(const std::vector<Proj<C>>& proj, size_t nthreads, uint8_t* out_xy, uint8_t* out_inf) {
-    using F = Field<C>;
-    using G = Group<C>;
-    constexpr int N = C::N;
-    size_t n = proj.size();
-    std::vector<Fe<C::NL>> prefix(n);
-    for (size_t t = 0; t < nthreads; t++) {
-        typename F::M1 acc = F::one();
-        for (size_t j = t; j < n; j += nthreads) {
-            prefix[j] = acc.e;
-            if (!F::is_zero(G::m(proj[j].z))) acc = F::mul(acc, G::m(proj[j].z));
-        }
-        typename F::M1 inv = F::inv(acc);
-        if (n <= t) continue;
-        size_t last = t + ((n - 1 - t) / nthreads) * nthreads;
-        for (size_t j = last;; j -= nthreads) {
-            const Proj<C>& p = proj[j];
-            if (F::is_zero(G::m(p.z))) {
-                std::memset(out_xy + j * 2 * WireBytes<C>::value, 0, 2 * WireBytes<C>::value);
-                out_inf[j] = 1;
-            } else {
-                typename F::M1 zinv = F::mul(G::m(prefix[j]), inv);
-                inv = F::mul(inv, G::m(p.z));
-                F::to_bytes(out_xy + j * 2 * WireBytes<C>::value, F::mul(G::m(p.x), zinv));
-                F::to_bytes(out_xy + j * 2 * WireBytes<C>::value + WireBytes<C>::value, F::mul(G::m(p.y), zinv));
-                out_inf[j] = 0;
-            }
-            if (j < nthreads) break;
-        }
-    }
-}
-
 template <class C>
 bool load_scalar(uint32_t* k, const uint8_t* be) {
     load_be_wire<C>(k, be);
@@ -307,7 +274,7 @@ int batch_mul_base(int w, const uint8_t* scalars, size_t n, size_t nthreads, uin
         if (!load_scalar<C>(k, scalars + i * WireBytes<C>::value)) return -2;
         proj[i] = fixed_base_one<C>(table, k);
     }
-    normalize<C>(proj, nthreads ? nthreads : 1, out_xy, out_inf);
+    ecgpu_host::normalize<C, NORM_WIRE>(proj, nthreads ? nthreads : 1, out_xy, out_inf);    // k_normalize's own lane body
     return 0;
 }
 
@@ -325,7 +292,7 @@ int batch_mul(const uint8_t* scalars, const uint8_t* pxy, const uint8_t* pinf, s
         if (!G::on_curve(a, b)) return -3;
         proj[i] = var_base_one<C>(a, k);
     }
-    normalize<C>(proj, nthreads ? nthreads : 1, out_xy, out_inf);
+    ecgpu_host::normalize<C, NORM_WIRE>(proj, nthreads ? nthreads : 1, out_xy, out_inf);    // k_normalize's own lane body
     return 0;
 }
 
@@ -370,7 +337,7 @@ int batch_mul_base_ct(const uint8_t* scalars, size_t n, uint8_t* out_xy, uint8_t
         if (!load_scalar<C>(k, scalars + i * WireBytes<C>::value)) return -2;
         proj[i] = fixed_base_mul_ct<C>(k, lut, Group<C>::curve_b());
     }
-    normalize<C>(proj, 1, out_xy, out_inf);
+    ecgpu_host::normalize<C, NORM_WIRE>(proj, 1, out_xy, out_inf);
     return 0;
 }
 template <class C>
@@ -390,7 +357,7 @@ int batch_mul_ct(const uint8_t* scalars, const uint8_t* pxy, const uint8_t* pinf
         VarTabLocal<C> tab;
         proj[i] = var_base_mul_ct<C>(p, k, b, tab);
     }
-    normalize<C>(proj, 1, out_xy, out_inf);
+    ecgpu_host::normalize<C, NORM_WIRE>(proj, 1, out_xy, out_inf);
     return 0;
 }
 
@@ -843,9 +810,7 @@ int table_rule_check(int w, int j, uint32_t e, uint8_t* out_xy) {
     return inf;
 }
 
-#define DISPATCH(curve, fn, args)                                                                                   \
-    switch (curve) { case 0: return fn<K256Params> args; case 1: return fn<P256Params> args; case 2: return fn<P384Params> args; \
-                     case 3: return fn<Sm2Params> args; case 4: return fn<P224Params> args; case 5: return fn<P192Params> args; case 6: return fn<P521Params> args; case 7: return fn<Bp256Params> args; case 8: return fn<Bp384Params> args; case 9: return fn<Bp256t1Params> args; case 10: return fn<Bp384t1Params> args; case 11: return fn<Bign256Params> args; default: return -1; }
+#define DISPATCH ECGPU_HOST_DISPATCH
 
 }  // namespace
 
@@ -885,6 +850,14 @@ int hc_batch_mul_base(int curve, int w, const uint8_t* s, size_t n, size_t nthre
 int hc_batch_mul(int curve, const uint8_t* s, const uint8_t* p, const uint8_t* pi, size_t n, size_t nthreads, uint8_t* o,
                  uint8_t* oi) {
     DISPATCH(curve, batch_mul, (s, p, pi, n, nthreads, o, oi))
+}
+// the lane bodies of k_normalize (mode 0: x || y + identity flags, 2: x + SEC1 tags; records X || Y || Z as given) and of
+// k_scalar_batch_inv, `nthreads` lanes
+int hc_normalize(int curve, int mode, const uint8_t* xyz, size_t n, size_t nthreads, uint8_t* out, uint8_t* flags) {
+    DISPATCH(curve, ecgpu_host::normalize_xyz, (mode, xyz, n, nthreads, out, flags))
+}
+int hc_scalar_batch_inv(int curve, const uint8_t* in, size_t n, size_t nthreads, uint8_t* out) {
+    DISPATCH(curve, ecgpu_host::scalar_batch_inv, (in, n, nthreads, out))
 }
 int hc_batch_mul_base_ct(int curve, const uint8_t* s, size_t n, uint8_t* o, uint8_t* oi) {
     DISPATCH(curve, batch_mul_base_ct, (s, n, o, oi))

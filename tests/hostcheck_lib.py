@@ -17,7 +17,7 @@ _lib = None
 
 def build():
     import fcntl
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_selftest_raw.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
+    deps = [SRC, os.path.join(HERE, "hostcheck", "batchinv_host.h")] + [os.path.join(CSRC, f) for f in ("ecgpu_batchinv.h", "ecgpu_xyz.h", "ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_selftest_raw.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
 
     def fresh():
         return os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps)
@@ -132,6 +132,27 @@ def batch_mul(curve, scalars, pxy, pinf=None, nthreads=1):
     inf = np.zeros(max(n, 1), np.uint8)
     rc = lib().hc_batch_mul(curve, _p(s), _p(p), _p(pi), ctypes.c_size_t(n), ctypes.c_size_t(nthreads), _p(out), _p(inf))
     return rc, out, inf[:n]
+
+
+def normalize(curve, mode, xyz, nthreads):
+    """The lane body of k_normalize on `nthreads` lanes over records X || Y || Z taken as they are.  mode 0 -> (x || y records,
+    identity flags); mode 2 -> (x records, SEC1 tags)."""
+    p = _a(xyz)
+    n = p.size // (3 * L[curve])
+    out = np.zeros(n * (2 if mode == 0 else 1) * L[curve], np.uint8)
+    flags = np.full(n, 0xEE, np.uint8)
+    rc = lib().hc_normalize(curve, mode, _p(p), ctypes.c_size_t(n), ctypes.c_size_t(nthreads), _p(out), _p(flags))
+    assert rc == 0, rc
+    return out, flags
+
+
+def scalar_batch_inv(curve, scalars, nthreads):
+    """The lane body of k_scalar_batch_inv on `nthreads` lanes: n scalars in, n out."""
+    s = _a(scalars)
+    n = s.size // L[curve]
+    out = np.full(n * L[curve], 0xEE, np.uint8)
+    assert lib().hc_scalar_batch_inv(curve, _p(s), ctypes.c_size_t(n), ctypes.c_size_t(nthreads), _p(out)) == 0
+    return out
 
 
 def batch_mul_base_ct(curve, scalars):

@@ -1,54 +1,22 @@
 // hostcheck_xyz_var.cpp — TEST INFRASTRUCTURE.  The lane body of the projective-to-affine conversion kernel of the
 // variable-time _xyz forms (k_xyz_affine, csrc/ecgpu_kernels.h; its body xyz_affine_lane, csrc/ecgpu_xyz.h) compiled with g++,
-// every lane of a launch run in turn with the kernel's record stride, so that it can be checked against the oracle without a
-// GPU.  Also the GPU tests' record generator: affine points rescaled by random z (X = x z, Y = y z, Z = z), on CPU threads.
+// every lane of a launch run in turn with the kernel's record stride (../hostcheck/batchinv_host.h), so that it can be checked
+// against the oracle without a GPU.  Also the GPU tests' record generator: affine points rescaled by random z (X = x z, Y = y z, Z = z), on CPU threads.
 // Nothing here is linked into libecgpu.so.
 #include <cstring>
 #include <thread>
 #include <vector>
 
-#include "../../elliptic-curves_amd/csrc/ecgpu_xyz.h"
+#include "../hostcheck/batchinv_host.h"
 
 using namespace ecgpu;
 
 namespace {
 
 template <class C>
-struct HostIo {
-    static constexpr int WB = WireBytes<C>::value, NS = Field<C>::NS;
-    const uint8_t* xyz;
-    uint32_t* prefix;
-    uint8_t* out_xy;
-    uint8_t* out_inf;
-    uint8_t* ok;
-    void load_z(size_t j, uint32_t* cz) const { load_be_wire<C>(cz, xyz + j * 3 * WB + 2 * WB); }
-    void load_xyz(size_t j, uint32_t* cx, uint32_t* cy, uint32_t* cz) const {
-        load_be_wire<C>(cx, xyz + j * 3 * WB);
-        load_be_wire<C>(cy, xyz + j * 3 * WB + WB);
-        load_be_wire<C>(cz, xyz + j * 3 * WB + 2 * WB);
-    }
-    void put_prefix(size_t j, const uint32_t* w) const { std::memcpy(prefix + j * NS, w, NS * 4); }
-    void get_prefix(size_t j, uint32_t* w) const { std::memcpy(w, prefix + j * NS, NS * 4); }
-    void put_affine(size_t j, const uint32_t* x, const uint32_t* y, bool ident) const {
-        store_be_wire<C>(out_xy + j * 2 * WB, x);
-        store_be_wire<C>(out_xy + j * 2 * WB + WB, y);
-        out_inf[j] = ident ? 1 : 0;
-    }
-    void verdict(size_t j, bool good) { ok[j] = good ? 1 : 0; }
-};
-
-// nthreads = 0: the lanes of launch_xyz_affine (ecgpu_inst_base.hip) for n records
-template <class C>
 int xyz_affine(const uint8_t* xyz, size_t n, size_t nthreads, uint8_t* out_xy, uint8_t* out_inf, uint8_t* ok) {
-    if (n == 0) return 0;
-    if (nthreads == 0) {
-        size_t k = (n + 65535) / 65536;
-        if (k > 64) k = 64;
-        nthreads = (n + k - 1) / k;
-    }
-    std::vector<uint32_t> prefix(n * Field<C>::NS);
-    HostIo<C> io{xyz, prefix.data(), out_xy, out_inf, ok};
-    for (size_t t = 0; t < nthreads; t++) xyz_affine_lane<C>(t, n, nthreads, io);
+    if (n == 0 || nthreads == 0) return n == 0 ? 0 : -1;
+    ecgpu_host::xyz_affine<C>(xyz, n, nthreads, out_xy, out_inf, ok);
     return 0;
 }
 
@@ -96,15 +64,13 @@ int rescale(const uint8_t* xy, const uint8_t* inf, size_t n, uint64_t seed, int 
     return 0;
 }
 
-#define DISPATCH(curve, fn, args)                                                                                   \
-    switch (curve) { case 0: return fn<K256Params> args; case 1: return fn<P256Params> args; case 2: return fn<P384Params> args; \
-                     case 3: return fn<Sm2Params> args; case 4: return fn<P224Params> args; case 5: return fn<P192Params> args; case 6: return fn<P521Params> args; case 7: return fn<Bp256Params> args; case 8: return fn<Bp384Params> args; case 9: return fn<Bp256t1Params> args; case 10: return fn<Bp384t1Params> args; case 11: return fn<Bign256Params> args; default: return -1; }
+#define DISPATCH ECGPU_HOST_DISPATCH
 
 }  // namespace
 
 extern "C" {
 
-// the conversion of n records by `nthreads` lanes (0: the launch's own lane count); ok[i] = 0 for a bad record
+// the conversion of n records by `nthreads` lanes; ok[i] = 0 for a bad record
 int hx_xyz_affine(int curve, const uint8_t* xyz, size_t n, size_t nthreads, uint8_t* out_xy, uint8_t* out_inf, uint8_t* ok) {
     DISPATCH(curve, xyz_affine, (xyz, n, nthreads, out_xy, out_inf, ok))
 }

@@ -39,8 +39,8 @@ def var_geometry(n):
 
 
 def chain(t, n, T):
-    """The records of lane t, in the order of the forward pass (csrc/ecgpu_kernels.h:397, csrc/ecgpu_xyz.h:42-49,
-    csrc/ecgpu_ecdsa.h:47)."""
+    """The records of lane t, in the order of the forward pass (csrc/ecgpu_kernels.h:420; k_xyz_affine and
+    k_scalar_batch_inv: batch_inv_lane's walk, csrc/ecgpu_batchinv.h:24-35 and :54)."""
     return np.arange(t, n, T, dtype=np.int64)
 
 

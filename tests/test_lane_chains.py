@@ -1,12 +1,19 @@
 """Degenerate records at every position of a lane's record chain, without a GPU: the geometry and planting helper
-(tests/lane_chains.py), the sizes of tests/test_gpu_lane_chains.py, and the lane body of k_xyz_affine compiled for the CPU
-(tests/hostcheck_xyz_var, `nthreads` lanes) with planted Z = 0 and off-curve records against a big-integer `to_affine`."""
+(tests/lane_chains.py), the sizes of tests/test_gpu_lane_chains.py, and the lane bodies of k_xyz_affine, k_normalize and
+k_scalar_batch_inv — three policies of one chain skeleton, csrc/ecgpu_batchinv.h — compiled for the CPU (tests/hostcheck_xyz_var,
+tests/hostcheck; `nthreads` lanes) with planted degenerate and off-curve records against big-integer arithmetic, once more in a
+stand-alone program under AddressSanitizer + UBSan."""
+import fcntl
 import itertools
+import os
 import random
+import struct
+import subprocess
 
 import numpy as np
 import pytest
 
+import hostcheck_lib
 import lane_chains as lc
 import pyec
 import test_gpu_lane_chains as gpu_file
@@ -296,3 +303,177 @@ def test_a_bad_record_fails_alone_wherever_it_sits(hx, name):
         assert np.nonzero(ok == 0)[0].tolist() == [j], (name, j)
         keep = np.arange(n) != j
         assert np.array_equal(got[keep], good[0][keep]) and np.array_equal(ginf[keep], good[1][keep]), (name, j)
+
+
+# ---- the lane bodies of k_normalize and k_scalar_batch_inv on the CPU -------------------------------------------------------------
+# Expectations from Python integers alone: pow(Z, -1, p), pow(a, -1, n).
+
+NORM_MODES = {"wire": 0, "compressed": 2}                     # NORM_WIRE, NORM_COMPRESSED (csrc/ecgpu_batchinv.h)
+N_SUB, T_SUB = 11, 4                                          # chains of 3, 3, 3, 2
+N_LONG, M_LONG = 323, 13
+
+
+def subsets():
+    """the 8 x 4 subsets of the records of lane 1 (3 records) and lane 3 (2 records) of 11 records on 4 lanes"""
+    recs = lc.chain(1, N_SUB, T_SUB).tolist() + lc.chain(3, N_SUB, T_SUB).tolist()
+    assert recs == [1, 5, 9, 3, 7]
+    return [[j for hit, j in zip(bits, recs) if hit] for bits in itertools.product((0, 1), repeat=5)]
+
+
+def normalized(c, mode, recs):
+    """-> (rows, flags) of k_normalize in `mode` for (X, Y, Z) integer triples"""
+    rows, flags = [], []
+    for r in recs:
+        xy, inf = to_affine(c, *r)
+        rows.append(xy if mode == 0 else xy[: c.L])
+        flags.append(inf if mode == 0 else 0 if inf else 2 + (int.from_bytes(xy[c.L:], c.order) & 1))
+    return np.frombuffer(b"".join(rows), np.uint8).reshape(len(recs), -1), np.array(flags, np.uint8)
+
+
+def xyz_bytes(c, recs):
+    return b"".join(enc_xyz(c, *r) for r in recs)
+
+
+def subset_records(c, rng):
+    """[(records, planted)]: the 32 subsets as Z = 0 records under arbitrary X, Y among ordinary ones"""
+    base = [ordinary(c, rng) for _ in range(N_SUB)]
+    out = []
+    for hit in subsets():
+        recs = list(base)
+        for j in hit:
+            recs[j] = (rng.randrange(1, c.p), rng.randrange(1, c.p), 0)
+        out.append((recs, hit))
+    return out
+
+
+@pytest.mark.parametrize("mode", sorted(NORM_MODES))
+@pytest.mark.parametrize("name", XYZ_CURVES)
+def test_normalize_body_every_subset_of_identities_on_a_chain(name, mode):
+    """The shape of test_every_subset_of_identities_on_a_chain through the lane body of k_normalize, x || y and compressed output."""
+    c = pyec.CURVES[name]
+    for recs, hit in subset_records(c, random.Random(0x2A5E + c.cid)):
+        got, gflag = hostcheck_lib.normalize(c.cid, NORM_MODES[mode], xyz_bytes(c, recs), T_SUB)
+        want, wflag = normalized(c, NORM_MODES[mode], recs)
+        bad = np.nonzero((got.reshape(N_SUB, -1) != want).any(axis=1) | (gflag != wflag))[0]
+        assert bad.size == 0, (name, mode, hit, "record %d = lane %d, position %d" % (bad[0], bad[0] % T_SUB, bad[0] // T_SUB))
+
+
+@pytest.mark.parametrize("mode", sorted(NORM_MODES))
+@pytest.mark.parametrize("name", XYZ_CURVES)
+@pytest.mark.parametrize("T", [6, 22])
+def test_normalize_body_planted_identities_on_long_chains(name, T, mode):
+    """n = 323 on 6 and 22 lanes with the classes of lane_chains.plant, as test_planted_identities_on_long_chains."""
+    c = pyec.CURVES[name]
+    tab = xyz_table(c, random.Random(0x2A5F + c.cid), M_LONG)
+    idx, rep = lc.plant(N_LONG, T, M_LONG, (0, 1, 2), 0x52 + c.cid)
+    assert {"first", "middle", "last", "adjacent", "ragged-last", "record n-1"} <= set(rep["classes"]) and (T == 6 or not rep["absent"])
+    recs = [tab[j] for j in idx]
+    got, gflag = hostcheck_lib.normalize(c.cid, NORM_MODES[mode], xyz_bytes(c, recs), T)
+    want, wflag = normalized(c, NORM_MODES[mode], recs)
+    assert lc.first_mismatch(got, want, rep, name) is None, lc.first_mismatch(got, want, rep, name)
+    assert lc.first_mismatch(gflag, wflag, rep, name) is None, lc.first_mismatch(gflag, wflag, rep, name)
+    assert (wflag == 0).sum() >= 7 if mode == "compressed" else wflag.sum() >= 7
+
+
+def scalar_degenerates(c):
+    return [0, c.n, 2 ** (8 * c.L) - 1]
+
+
+def inverses(c, xs):
+    """k_scalar_batch_inv's contract: 0 for an element outside [1, n - 1], the inverse modulo n otherwise"""
+    return b"".join((pow(x, -1, c.n) if 0 < x < c.n else 0).to_bytes(c.L, c.order) for x in xs)
+
+
+def scalar_bytes(c, xs):
+    return b"".join(x.to_bytes(c.L, c.order) for x in xs)
+
+
+def subset_scalars(c, rng):
+    base = [rng.randrange(1, c.n) for _ in range(N_SUB)]
+    base[0], base[2] = 1, c.n - 1                             # the ends of the range are ordinary elements
+    out = []
+    for k, hit in enumerate(subsets()):
+        xs = list(base)
+        for i, j in enumerate(hit):
+            xs[j] = scalar_degenerates(c)[(i + k) % 3]
+        out.append((xs, hit))
+    return out
+
+
+def long_scalars(c, rng, T, seed):
+    tab = scalar_degenerates(c) + [1, c.n - 1] + [rng.randrange(1, c.n) for _ in range(M_LONG - 5)]
+    idx, rep = lc.plant(N_LONG, T, M_LONG, (0, 1, 2), seed)
+    return [tab[j] for j in idx], rep
+
+
+@pytest.mark.parametrize("name", sorted(pyec.CURVES))
+def test_scalar_body_every_subset_of_degenerates_on_a_chain(name):
+    """0, n and 2^(8L) - 1 at every subset of positions of a length-3 and a length-2 chain: 0 for those, the inverse modulo n for
+    every other element of the lane."""
+    c = pyec.CURVES[name]
+    for xs, hit in subset_scalars(c, random.Random(0x3A5E + c.cid)):
+        got = hostcheck_lib.scalar_batch_inv(c.cid, scalar_bytes(c, xs), T_SUB).reshape(N_SUB, c.L)
+        want = np.frombuffer(inverses(c, xs), np.uint8).reshape(N_SUB, c.L)
+        bad = np.nonzero((got != want).any(axis=1))[0]
+        assert bad.size == 0, (name, hit, "record %d = lane %d, position %d" % (bad[0], bad[0] % T_SUB, bad[0] // T_SUB))
+
+
+@pytest.mark.parametrize("name", sorted(pyec.CURVES))
+@pytest.mark.parametrize("T", [6, 22])
+def test_scalar_body_planted_degenerates_on_long_chains(name, T):
+    c = pyec.CURVES[name]
+    xs, rep = long_scalars(c, random.Random(0x3A5F + c.cid), T, 0x53 + c.cid)
+    assert {"first", "middle", "last", "adjacent", "ragged-last", "record n-1"} <= set(rep["classes"]) and (T == 6 or not rep["absent"])
+    got = hostcheck_lib.scalar_batch_inv(c.cid, scalar_bytes(c, xs), T)
+    want = np.frombuffer(inverses(c, xs), np.uint8)
+    assert lc.first_mismatch(got, want, rep, name) is None, lc.first_mismatch(got, want, rep, name)
+    assert sum(1 for x in xs if not 0 < x < c.n) >= 7
+
+
+# ---- the three bodies in a stand-alone program under the sanitizers ------------------------------------------------------------------
+
+HC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostcheck")
+SAN_SRC, SAN_PROG = os.path.join(HC, "batchinv_san.cpp"), os.path.join(HC, "batchinv_san")
+
+
+def build_san():
+    csrc = os.path.join(os.path.dirname(os.path.dirname(HC)), "elliptic-curves_amd", "csrc")
+    deps = [SAN_SRC, os.path.join(HC, "batchinv_host.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")]
+    with open(SAN_PROG + ".lock", "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        if not os.path.exists(SAN_PROG) or os.path.getmtime(SAN_PROG) < max(os.path.getmtime(d) for d in deps):
+            tmp = SAN_PROG + ".tmp.%d" % os.getpid()
+            # (the runtimes linked into the program itself: it needs no preload)
+            subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wno-unknown-pragmas", "-fsanitize=undefined,address",
+                                   "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-o", tmp, SAN_SRC])
+            os.replace(tmp, SAN_PROG)
+
+
+def san_case(kind, c, mode, n, T, data, want):
+    return struct.pack("<7I", kind, c.cid, mode, n, T, len(data), len(want)) + data + want
+
+
+def test_sanitized_standalone_program():
+    """AddressSanitizer + UBSan on the three lane bodies over buffers of exactly n records: both shapes, outputs compared inside
+    the program with the values computed here."""
+    build_san()
+    cases = []
+    for name in sorted(pyec.CURVES):
+        c = pyec.CURVES[name]
+        rng = random.Random(0x4A5E + c.cid)
+        shapes = [(xs, T_SUB) for xs, _ in subset_scalars(c, rng)[::5]] + [(long_scalars(c, rng, T, 0x54 + c.cid)[0], T) for T in (6, 22)]
+        cases += [san_case(2, c, 0, len(xs), T, scalar_bytes(c, xs), inverses(c, xs)) for xs, T in shapes]
+        if name not in XYZ_CURVES:
+            continue
+        tab = xyz_table(c, rng, M_LONG)
+        shapes = [(recs, T_SUB) for recs, _ in subset_records(c, rng)[::5]]
+        shapes += [([tab[j] for j in lc.plant(N_LONG, T, M_LONG, (0, 1, 2), 0x55 + c.cid)[0]], T) for T in (6, 22)]
+        for recs, T in shapes:
+            n = len(recs)
+            for mode in NORM_MODES.values():
+                rows, flags = normalized(c, mode, recs)
+                cases.append(san_case(0, c, mode, n, T, xyz_bytes(c, recs), rows.tobytes() + flags.tobytes()))
+            rows, flags = normalized(c, 0, recs)              # every record here is on the curve or an identity: verdict 1
+            cases.append(san_case(1, c, 0, n, T, xyz_bytes(c, recs), rows.tobytes() + flags.tobytes() + bytes([1]) * n))
+    r = subprocess.run([SAN_PROG], input=b"".join(cases), capture_output=True)
+    assert r.returncode == 0 and r.stdout.decode().strip() == "%d cases equal" % len(cases), (r.returncode, r.stdout[-300:], r.stderr[-3000:])

@@ -14,6 +14,7 @@ import sys
 import numpy as np
 import pytest
 
+import lane_chains
 import oracle_lib
 import pyec
 
@@ -122,8 +123,8 @@ def test_xyz_affine_record_codecs_move_whole_words():
 # ---- the lane body on the CPU -------------------------------------------------------------------------------------------
 
 def build_helper():
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("ecgpu_xyz.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h",
-                                                     "ecgpu_point.h", "ecgpu_modinv.h")]
+    deps = [SRC, os.path.join(ROOT, "tests", "hostcheck", "batchinv_host.h")] + [os.path.join(CSRC, f) for f in (
+        "ecgpu_xyz.h", "ecgpu_batchinv.h", "ecgpu_scalar.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_modinv.h")]
 
     def fresh():
         return os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps)
@@ -143,7 +144,10 @@ def hx():
 
 
 def convert(hx, c, xyz, nthreads=0):
+    """nthreads = 0: the lanes of launch_xyz_affine for n records (lane_chains.norm_geometry)"""
     n = len(xyz) // (3 * c.L)
+    if nthreads == 0 and n:
+        nthreads = lane_chains.norm_geometry(n)[1]
     p = np.frombuffer(xyz, np.uint8).copy()
     out, inf, ok = np.zeros(n * 2 * c.L, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
     assert hx.hx_xyz_affine(c.cid, p.ctypes.data_as(_u8p), ctypes.c_size_t(n), ctypes.c_size_t(nthreads), out.ctypes.data_as(_u8p),
