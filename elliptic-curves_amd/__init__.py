@@ -50,7 +50,7 @@ ABI_SYMBOLS = [
     "ecgpu_msm_parts_bytes", "ecgpu_msm_plan_window", "ecgpu_msm_parts_dev", "ecgpu_msm_finish_dev",
     "ecgpu_group_init", "ecgpu_group_destroy", "ecgpu_group_size", "ecgpu_group_ctx", "ecgpu_group_last_error",
     "ecgpu_group_exchange", "ecgpu_group_set_msm_window", "ecgpu_group_msm", "ecgpu_group_msm_dev",
-    "ecgpu_group_batch_mul_base", "ecgpu_group_batch_mul", "ecgpu_selftest_field", "ecgpu_selftest_point",
+    "ecgpu_group_batch_mul_base", "ecgpu_group_batch_mul", "ecgpu_selftest_field", "ecgpu_selftest_point", "ecgpu_selftest_point_raw",
     "ecgpu_sm2dsa_verify_batch", "ecgpu_sm2dsa_verify_batch_dev", "ecgpu_set_async", "ecgpu_synchronize",
     "ecgpu_ecdsa_recover_batch", "ecgpu_ecdsa_recover_batch_dev",
     "ecgpu_sm2dsa_verify_msg_batch", "ecgpu_sm2dsa_verify_msg_batch_dev",
@@ -150,6 +150,10 @@ def _field_bytes(curve):
     if curve not in FIELD_BYTES:
         raise EcgpuError(ERR_CURVE, "unknown curve id %r" % (curve,))
     return FIELD_BYTES[curve]
+
+
+# limbs per field element in registers (NL of csrc/ecgpu_field_consts.h), by curve id: the record unit of Engine.selftest_point_raw
+POINT_RAW_LIMBS = {0: 9, 1: 10, 2: 15, 3: 10, 4: 9, 5: 8, 6: 20, 7: 10, 8: 15, 9: 10, 10: 15, 11: 10}
 
 
 def _host(a):
@@ -814,6 +818,21 @@ class Engine:
         self._chk(self._lib.ecgpu_selftest_point(self._ctx, curve, int(op), _hp(P), _hp(PI), _hp(Q), _hp(QI), ctypes.c_size_t(n),
                                                  _hp(out), _hp(inf)))
         return out, inf
+
+    def selftest_point_raw(self, curve, op, p, q=None):
+        """The point formulas on raw limbs (csrc/ecgpu_selftest_point_raw.h): p, q and the result are uint32 arrays of n records
+        of four coordinate slots of NL limbs each, taken and returned as they are."""
+        P = np.ascontiguousarray(p, dtype=np.uint32).reshape(-1)
+        Q = None if q is None else np.ascontiguousarray(q, dtype=np.uint32).reshape(-1)
+        rec = 4 * POINT_RAW_LIMBS[curve]
+        n = P.size // rec
+        _need("p", P.view(np.uint8), n * rec * 4)
+        if Q is not None:
+            _need("q", Q.view(np.uint8), n * rec * 4)
+        out = np.zeros(n * rec, np.uint32)
+        self._chk(self._lib.ecgpu_selftest_point_raw(self._ctx, curve, int(op), _hp(P.view(np.uint8)), _hp(None if Q is None else Q.view(np.uint8)),
+                                                     ctypes.c_size_t(n), _hp(out.view(np.uint8))))
+        return out.reshape(n, rec)
 
     # ---- device-resident operations (torch uint8 CUDA tensors or raw device pointers) ----
     def mul_by_generator_dev(self, curve, d_scalars, n, d_out_xy, d_out_inf=None, constant_time=False):

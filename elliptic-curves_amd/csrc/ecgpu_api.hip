@@ -2821,6 +2821,23 @@ int ecgpu_selftest_point(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p_xy,
                   }, STAGE_WHOLE);
 }
 
+int ecgpu_selftest_point_raw(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p, const uint8_t* q, size_t n, uint8_t* out) {
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(n && (!p || !out))) return h.rc;
+    if (n == 0) return ECGPU_OK;
+    size_t rec = 0;                                           // four slots of NL 32-bit limbs
+    dispatch(curve, [&](auto c) { rec = 16 * (size_t) decltype(c)::NL; return (int)ECGPU_OK; });
+    return staged(ctx, n, {{p, &ctx->in0, rec}, {q, &ctx->in1, rec}}, {{out, &ctx->out0, rec}}, [&](auto in, auto o, size_t m) {
+        int rc = reset_status(ctx);
+        if (rc != ECGPU_OK) return rc;
+        rc = dispatch(curve, [&](auto c) {
+            launch_selftest_point_raw<decltype(c)>(ctx->stream, op, (const uint32_t*)in[0], (const uint32_t*)in[1], m, (uint32_t*)o[0], ctx->d_status);
+            return (int)ECGPU_OK;
+        });
+        return rc != ECGPU_OK ? rc : finish(ctx);
+    }, STAGE_WHOLE);
+}
+
 int ecgpu_valu_probe(ecgpu_ctx* ctx, int which, double* ops_per_sec) {
     if (!check_ctx(ctx) || !ops_per_sec) return ECGPU_ERR_ARG;
     int rc;

@@ -148,5 +148,9 @@ template <> void launch_selftest_point<CurveT>(hipStream_t s, int op, const uint
     hipLaunchKernelGGL(k_selftest_point<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, op, pxy, pinf, qxy, qinf, n, out_xy, out_inf,
                        status);
 }
+template <> void launch_selftest_point_raw<CurveT>(hipStream_t s, int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out,
+                                                   int* status) {
+    hipLaunchKernelGGL(k_selftest_point_raw<CurveT>, dim3(grid_for(n)), dim3(BLOCK), 0, s, op, p, q, n, out, status);
+}
 
 }  // namespace ecgpu

@@ -86,6 +86,9 @@ template <class C> void launch_ecdsa_finish(hipStream_t s, const uint8_t* r_xy, 
 template <class C> void launch_selftest_field(hipStream_t s, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out, int* status);
 template <class C> void launch_selftest_point(hipStream_t s, int op, const uint8_t* pxy, const uint8_t* pinf, const uint8_t* qxy,
                                               const uint8_t* qinf, size_t n, uint8_t* out_xy, uint8_t* out_inf, int* status);
+// records of 4 NL limbs in and out (ecgpu_selftest_point_raw.h); q may be null
+template <class C> void launch_selftest_point_raw(hipStream_t s, int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out,
+                                                  int* status);
 // ops 20 - 26 of ecgpu_selftest_point: the cross-lane code behind the MSM's buckets (group "msm", ecgpu_selftest_msm.h)
 template <class C> void launch_selftest_msm(hipStream_t s, int op, const uint8_t* pxy, const uint8_t* pinf, const uint8_t* qxy,
                                             const uint8_t* qinf, size_t n, uint8_t* out_xy, uint8_t* out_inf, int* status);

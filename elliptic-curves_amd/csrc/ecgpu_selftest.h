@@ -9,6 +9,7 @@
 #include "ecgpu_kernels.h"
 #include "ecgpu_rows.h"
 #include "ecgpu_selftest_raw.h"
+#include "ecgpu_selftest_point_raw.h"
 
 namespace ecgpu {
 
@@ -252,6 +253,27 @@ __global__ void __launch_bounds__(BLOCK) k_selftest_point(int op, const uint8_t*
         store_wire<C>(out_xy + i * (2 * WB) + WB, w);
         out_inf[i] = 0;
     }
+}
+
+// point formulas on coordinates taken limb by limb (ecgpu_selftest_point_raw.h, where the ops are listed): records of four slots of
+// NL 32-bit words, the words are the limbs — no unpack, no check — and the result leaves the same way, no inversion.  One lane
+// per record, any n >= 1; q may be absent (zeros).  A kernel of its own, so that the code objects of the kernels above stay what
+// they were; it contains the k256 assembly blocks (128 VGPRs or more, which __launch_bounds__(BLOCK) grants).
+template <class C>
+__global__ void __launch_bounds__(BLOCK) k_selftest_point_raw(int op, const uint32_t* __restrict__ p, const uint32_t* __restrict__ q, size_t n,
+                                                              uint32_t* __restrict__ out, int* status) {
+    constexpr int W = 4 * C::NL;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t wp[W], wq[W], wr[W];
+#pragma unroll
+    for (int t = 0; t < W; t++) {
+        wp[t] = p[i * W + t];
+        wq[t] = q ? q[i * W + t] : 0u;
+    }
+    if (!selftest_point_raw<C>(op, wp, wq, wr)) atomicOr(status, ST_BAD_SCALAR);
+#pragma unroll
+    for (int t = 0; t < W; t++) out[i * W + t] = wr[t];
 }
 
 }  // namespace ecgpu

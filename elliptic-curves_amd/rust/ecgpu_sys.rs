@@ -931,6 +931,15 @@ unsafe extern "C" {
         out_xy: *mut u8,
         out_inf: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_selftest_point_raw(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        op: c_int,
+        p: *const u8,
+        q: *const u8,
+        n: usize,
+        out: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_valu_probe(ctx: *mut EcgpuCtx, which: c_int, ops_per_sec: *mut f64) -> c_int;
     pub fn ecgpu_last_timing(ctx: *const EcgpuCtx, name: *const c_char, ms: *mut f64) -> c_int;
     pub fn ecgpu_set_timing(ctx: *mut EcgpuCtx, on: c_int) -> c_int;

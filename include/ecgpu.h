@@ -796,10 +796,29 @@ int ecgpu_sm2_pke_decrypt_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t 
  *   quad, P + Q of each quad's first lane in all four lanes; 24 the same on Group::add(P, Q) and Group::dbl(Q): P + 3 Q; 25 the
  *   workgroup-wide tree sum of P over 256 lanes in the workgroup's first record (the identity in the others).  The a = -3 sets:
  *   26 2^steps (P + Q) (P alone without q_xy) of the wave's first lane in every lane, by the Jacobian doubling shared by three lanes.
+ * ecgpu_selftest_point_raw: the point formulas on coordinates taken limb by limb (a kernel of its own; csrc/ecgpu_selftest_point_raw.h).
+ *   A record is four coordinate slots of NL little-endian 32-bit words each (NL limbs of B bits: 9 x 29 k256; 10 x 28 p256, sm2,
+ *   bp256, bp256t1, bign256; 15 x 27 p384, bp384, bp384t1; 9 x 27 p224; 8 x 26 p192; 20 x 27 p521), the words are the limbs of
+ *   the internal form as they are (the Montgomery form where the set has one): nothing is converted, range-checked or checked
+ *   against the curve, and out[i] comes back in the same layout with no inversion.  Slots: homogeneous X Y Z -, Jacobian X Y Z -,
+ *   XYZZ X Y ZZ ZZZ, affine x y - -.  q may be NULL (zeros).  Any n.
+ *     op  result        operation                           op  result        operation
+ *      0  homogeneous   add(P, Q)                            8  Jacobian      jac_madd(J, q)
+ *      1  homogeneous   add(P, -Q)                           9  Jacobian      jac_madd(J, -q)
+ *      2  homogeneous   add_mixed(P, q)                     10  homogeneous   jac_to_proj(J)
+ *      3  homogeneous   add_mixed(P, -q)                    11  XYZZ          xyzz_madd(S, q)
+ *      4  homogeneous   dbl(P)                              12  XYZZ          xyzz_madd(S, -q)
+ *      5  homogeneous   neg(P)                              13  XYZZ          xyzz_mmadd(p, q)
+ *      6  homogeneous   ct_dbl4(P) = 16 P                   14  homogeneous   xyzz_to_proj(S)
+ *      7  Jacobian      jac_dbl(J)                          17  first word    is_identity(P) as 0 / 1
+ *     15 | steps << 8   homogeneous   acc = dbl(add(acc, Q)), steps times from acc = P        (steps <= 64)
+ *     16 | steps << 8   Jacobian      acc = jac_madd(jac_dbl^4(acc), q), steps times from acc = J: the ladder step
+ *   The Jacobian and XYZZ formulas are the incomplete ones: outside their domain (a finite P != +-Q) the result means nothing.
  * ECGPU_ERR_POINT: an input >= p (field ops 0 - 21) / off the curve; ECGPU_ERR_SCALAR_RANGE: unknown op. */
 int ecgpu_selftest_field(ecgpu_ctx *ctx, int curve, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
 int ecgpu_selftest_point(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p_xy, const uint8_t *p_inf, const uint8_t *q_xy,
                          const uint8_t *q_inf, size_t n, uint8_t *out_xy, uint8_t *out_inf);
+int ecgpu_selftest_point_raw(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p, const uint8_t *q, size_t n, uint8_t *out);
 
 /* Integer-VALU roof probe: runs a dependency-free v_mad_u64_u32 stream on every CU and returns
  * the measured 32x32->64 multiply-add rate in operations per second (SURVEY.md §8d "peak to

@@ -20,6 +20,7 @@
 #include "../../elliptic-curves_amd/csrc/ecgpu_belt.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_verify.h"
 #include "../../elliptic-curves_amd/csrc/ecgpu_selftest_raw.h"
+#include "../../elliptic-curves_amd/csrc/ecgpu_selftest_point_raw.h"
 #include "batchinv_host.h"
 
 using namespace ecgpu;
@@ -159,6 +160,17 @@ int point_op(int op, const uint8_t* pxy, int pinf, const uint8_t* qxy, int qinf,
     default: return -1;
     }
     store_affine<C>(r, out, oinf);
+    return 0;
+}
+
+// the point formulas on raw limbs (ecgpu_selftest_point_raw.h; what the device runs as k_selftest_point_raw): n records of four
+// slots of NL 32-bit words in p and q (q may be null: zeros), n records out
+template <class C>
+int point_raw(int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out) {
+    constexpr int W = 4 * C::NL;
+    uint32_t zero[W] = {0};
+    for (size_t i = 0; i < n; i++)
+        if (!selftest_point_raw<C>(op, p + i * W, q ? q + i * W : zero, out + i * W)) return -1;
     return 0;
 }
 
@@ -840,6 +852,9 @@ int hc_field_chain(int curve, const uint8_t* a, const uint8_t* b, int steps, uin
 }
 int hc_point_op(int curve, int op, const uint8_t* p, int pi, const uint8_t* q, int qi, uint8_t* out, uint8_t* oi) {
     DISPATCH(curve, point_op, (op, p, pi, q, qi, out, oi))
+}
+int hc_point_raw(int curve, int op, const uint32_t* p, const uint32_t* q, size_t n, uint32_t* out) {
+    DISPATCH(curve, point_raw, (op, p, q, n, out))
 }
 int hc_on_curve(int curve, const uint8_t* xy) {
     DISPATCH(curve, on_curve, (xy))

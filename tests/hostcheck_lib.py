@@ -17,7 +17,7 @@ _lib = None
 
 def build():
     import fcntl
-    deps = [SRC, os.path.join(HERE, "hostcheck", "batchinv_host.h")] + [os.path.join(CSRC, f) for f in ("ecgpu_batchinv.h", "ecgpu_xyz.h", "ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_selftest_raw.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
+    deps = [SRC, os.path.join(HERE, "hostcheck", "batchinv_host.h")] + [os.path.join(CSRC, f) for f in ("ecgpu_batchinv.h", "ecgpu_xyz.h", "ecgpu_verify.h", "ecgpu_field.h", "ecgpu_params.h", "ecgpu_field_consts.h", "ecgpu_point.h", "ecgpu_recode.h", "ecgpu_varmul.h", "ecgpu_ctmul.h", "ecgpu_msm_chunk.h", "ecgpu_modinv.h", "ecgpu_fixedmul.h", "ecgpu_scalar.h", "ecgpu_selftest_raw.h", "ecgpu_selftest_point_raw.h", "ecgpu_sha256.h", "ecgpu_hash.h", "ecgpu_sm3.h", "ecgpu_belt.h")]
 
     def fresh():
         return os.path.exists(LIB) and all(os.path.getmtime(LIB) >= os.path.getmtime(d) for d in deps)
@@ -109,6 +109,24 @@ def point_op(curve, op, p_xy, p_inf=0, q_xy=None, q_inf=0):
     P, Q = _a(p_xy), _a(q_xy)
     assert lib().hc_point_op(curve, op, _p(P), int(p_inf), _p(Q), int(q_inf), _p(out), _p(inf)) == 0
     return bytes(out), int(inf[0])
+
+
+NL = {0: 9, 1: 10, 2: 15, 3: 10, 4: 9, 5: 8, 6: 20, 7: 10, 8: 15, 9: 10, 10: 15, 11: 10}
+
+
+def point_raw(curve, op, p, q=None):
+    """selftest_point_raw (csrc/ecgpu_selftest_point_raw.h) on n records of 4 NL limbs: uint32 arrays in, an (n, 4 NL) array out."""
+    P = np.ascontiguousarray(p, dtype=np.uint32).reshape(-1)
+    Q = None if q is None else np.ascontiguousarray(q, dtype=np.uint32).reshape(-1)
+    rec = 4 * NL[curve]
+    n = P.size // rec
+    assert P.size == n * rec and (Q is None or Q.size == P.size)
+    out = np.zeros(max(n, 1) * rec, np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    rc = lib().hc_point_raw(curve, int(op), P.ctypes.data_as(u32p), None if Q is None else Q.ctypes.data_as(u32p), ctypes.c_size_t(n),
+                            out.ctypes.data_as(u32p))
+    assert rc == 0, rc
+    return out[: n * rec].reshape(n, rec)
 
 
 def on_curve(curve, xy):
