@@ -20,6 +20,9 @@
 // The other curves (brainpoolP256r1: n = 0.66 * 2^256; p521: 521 bits in 544) do not rely on this: COMB_NEEDS_CHECK.
 // tests: comb_corner_scalars (tests/gpu_common.py) at W = 5, 15 and 17 (top window at bit 255) and, on a table pinned to each of
 // them, at the widths in use (16, 22, the widest): tests/test_gpu_comb_table.py, which also checks the table's entries as entries.
+// The two forms of the walk (below) change the control flow around the additions, not the additions or their order, so the argument
+// holds for both; zero digits at every window, alone in a wave and on all of its lanes: tests/test_gpu_fixed_trim.py, and lane by
+// lane on the CPU tests/test_hostcheck_fixed_trim.py.
 #pragma once
 
 #include "ecgpu_point.h"
@@ -50,6 +53,69 @@ ECGPU_HD Affine<C> load_entry(const Table& table, int window, uint32_t index) {
 template <class C>
 constexpr bool COMB_NEEDS_CHECK = C::ORDER[C::N - 1] < 0xF0000000u;
 
+// The scalar is consumed from the bottom: the low w bits (0 < w < 32) of the N-word value, which then moves down by w bits — one
+// funnel shift per word at a wave-uniform distance, where get_bits at a run-time position selects two words out of N.
+template <int N>
+ECGPU_HD uint32_t take_low_bits(uint32_t* k, int w) {
+    const uint32_t raw = k[0] & ((1u << w) - 1);
+#pragma unroll
+    for (int i = 0; i + 1 < N; i++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        k[i] = __builtin_amdgcn_alignbit(k[i + 1], k[i], (uint32_t)w);
+#else
+        k[i] = (uint32_t)((((uint64_t)k[i + 1] << 32) | k[i]) >> w);
+#endif
+    }
+    k[N - 1] >>= w;
+    return raw;
+}
+
+// whether `pred` holds on every active lane of the wave (a wave-uniform value); on the host a lane is alone
+ECGPU_HD bool wave_all(bool pred) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(!pred) == 0;
+#else
+    return pred;
+#endif
+}
+
+// whether the walk below has its fast path.  Not where COMB_NEEDS_CHECK holds: those curves read the folded scalar a second time,
+// so the shifted copy is eight more live registers, and k_fixed_base<Bp256Params> / <Bp256t1Params> went from 150 to 178 registers
+// and from three waves per SIMD to two with it (and <Bp384Params> from 223 to more than 256 with the digit taken one window
+// ahead).  Nor on the curves of another width: the gain is instructions, not time (profiles/fixed_trim/headline_ab.txt), and
+// k_fixed_base<P224Params, true> paid 19 registers for it (137 -> 156), <P384Params, true> 34 (222 -> 256, the last one before it
+// spills); on the eight-word curves that run it the cost is -2 .. +1.  The others keep the one loop, with get_bits, as it was.
+template <class C>
+constexpr bool COMB_FAST_WALK = !COMB_NEEDS_CHECK<C> && C::N == 8;
+
+// One window of the state machine: the entry of digit d != 0 of window j joins the sum.
+// state 0: nothing added yet; 1: acc = (x, y) affine (one entry); 2: acc in XYZZ coordinates
+template <class C, class Table>
+ECGPU_HD void comb_add(int& state, Xyzz<C>& acc, const Table& table, int j, int d, bool flip) {
+    using G = Group<C>;
+    Affine<C> q = load_entry<C>(table, j, (uint32_t)(d < 0 ? -d : d) - 1);
+    const bool neg = (d < 0) != flip;
+    if (state == 2) {
+        acc = G::xyzz_madd(acc, q, neg);
+    } else if (state == 1) {
+        Affine<C> a;
+        a.x = acc.x;
+        a.y = acc.y;
+        acc = G::xyzz_mmadd(a, q, neg);
+        state = 2;
+    } else {
+        if (neg) q.y = G::neg_coord(q.y);
+        acc.x = q.x;
+        acc.y = q.y;
+        state = 1;
+    }
+}
+
+// The walk over the windows has two forms that perform the same additions in the same order.  While every active lane of the wave
+// has a non-zero digit (with random scalars: always — a zero digit has probability 2^-w) nobody needs to know which kind of addition
+// comes next: window 0 loads the accumulator, window 1 is the affine + affine addition, and windows 2 .. nwin - 1 are a loop of
+// gather, unpack and xyzz_madd with the accumulator updated in place.  The first zero digit on any lane, at window j, sends the wave
+// to the state machine, which goes on at window j from (state, acc, carry, the scalar shifted so far) and handles every case.
 template <class C, class Table>
 ECGPU_HD Proj<C> fixed_base_mul(const uint32_t* k_in, const Table& table, int w, int nwin, const Fe<C::NL>& b) {
     using G = Group<C>;
@@ -59,30 +125,45 @@ ECGPU_HD Proj<C> fixed_base_mul(const uint32_t* k_in, const Table& table, int w,
     for (int i = 0; i < N; i++) k[i] = k_in[i];
     const bool flip = fold_scalar<N>(k, C::ORDER);
     uint32_t carry = 0;
-    // state 0: nothing added yet; 1: acc = (x, y) affine (one entry); 2: acc in XYZZ coordinates
     int state = 0;
     Xyzz<C> acc;
     acc.x = acc.y = acc.zz = acc.zzz = Field<C>::one().e;
+    if constexpr (!COMB_FAST_WALK<C>) {
 #pragma unroll 1
-    for (int j = 0; j < nwin; j++) {
-        int d = signed_window_step(get_bits<N>(k, j * w, w), w, &carry);
-        if (d != 0) {
-            Affine<C> q = load_entry<C>(table, j, (uint32_t)(d < 0 ? -d : d) - 1);
-            const bool neg = (d < 0) != flip;
-            if (state == 2) {
-                acc = G::xyzz_madd(acc, q, neg);
-            } else if (state == 1) {
-                Affine<C> a;
-                a.x = acc.x;
-                a.y = acc.y;
-                acc = G::xyzz_mmadd(a, q, neg);
-                state = 2;
-            } else {
-                if (neg) q.y = G::neg_coord(q.y);
-                acc.x = q.x;
-                acc.y = q.y;
-                state = 1;
+        for (int j = 0; j < nwin; j++) {
+            int d = signed_window_step(get_bits<N>(k, j * w, w), w, &carry);
+            if (d != 0) comb_add<C>(state, acc, table, j, d, flip);
+        }
+    } else {
+        uint32_t ks[N];             // what is left of the scalar above the windows taken so far
+#pragma unroll
+        for (int i = 0; i < N; i++) ks[i] = k[i];
+        // d is the digit of window j for as long as j < nwin
+        int j = 0;
+        int d = signed_window_step(take_low_bits<N>(ks, w), w, &carry);
+        if (wave_all(d != 0)) {
+            comb_add<C>(state, acc, table, 0, d, flip);                  // state 0 -> 1 (a literal on this path, as below)
+            j = 1;
+            if (nwin > 1) {
+                d = signed_window_step(take_low_bits<N>(ks, w), w, &carry);
+                if (wave_all(d != 0)) {
+                    comb_add<C>(state, acc, table, 1, d, flip);          // 1 -> 2
+                    j = 2;
+#pragma unroll 1
+                    while (j < nwin) {
+                        d = signed_window_step(take_low_bits<N>(ks, w), w, &carry);
+                        if (!wave_all(d != 0)) break;
+                        Affine<C> q = load_entry<C>(table, j, (uint32_t)(d < 0 ? -d : d) - 1);
+                        acc = G::xyzz_madd(acc, q, (d < 0) != flip);
+                        j++;
+                    }
+                }
             }
+        }
+#pragma unroll 1
+        while (j < nwin) {
+            if (d != 0) comb_add<C>(state, acc, table, j, d, flip);
+            if (++j < nwin) d = signed_window_step(take_low_bits<N>(ks, w), w, &carry);
         }
     }
     if (state == 0) return G::identity();

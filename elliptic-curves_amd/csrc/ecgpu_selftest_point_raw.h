@@ -18,6 +18,9 @@
 //   15 acc = dbl(add(acc, Q)), steps times, acc = P (homogeneous in and out)
 //   16 acc = jac_madd(jac_dbl^4(acc), q), steps times, acc = J: the ladder step of ecgpu_varmul.h (Jacobian in and out)
 //   17 is_identity(P) as 0 / 1 in the first word of the result
+//   19 the identity test of k_normalize's forward pass on the limbs of Z as they are (NormRec::classify, ecgpu_batchinv.h):
+//      Field::is_zero_short(m(Z)) as 0 / 1 in the first word and Field::is_zero(m(Z)) in the second (18 stays unknown: the
+//      op-range tests pin it)
 // False for an unknown operation.
 #pragma once
 
@@ -89,6 +92,10 @@ ECGPU_HD bool selftest_point_raw(int op, const uint32_t* p, const uint32_t* q, u
             put_j(J);
             break;
         case 17: o[0].v[0] = G::is_identity(P) ? 1u : 0u; break;
+        case 19:
+            o[0].v[0] = Field<C>::is_zero_short(G::m(P.z)) ? 1u : 0u;
+            o[0].v[1] = Field<C>::is_zero(G::m(P.z)) ? 1u : 0u;
+            break;
         default: known = false;
         }
     }

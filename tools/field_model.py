@@ -159,6 +159,34 @@ def k256_to_words_m1(a):
     return from_limbs(out, K_B)
 
 
+def k256_is_zero_m1(a):
+    """Field::k_is_zero<NORMED = true>: a = 0 (mod p) from the strict limbs that the two folds and the carry pass of k_to_words
+    leave — ONE fold here, value < 2^256 + 2^38: all limbs zero, or the limbs of p."""
+    r = list(a)
+    assert all(x < K_LB for x in r)
+    for _ in range(1):
+        carry = 0
+        for k in range(8):
+            v = chk32(r[k] + carry)
+            r[k] = v & K_MASK
+            carry = v >> K_B
+        v8 = chk32(r[8] + carry)
+        e = v8 >> 24
+        r[8] = v8 & 0xFFFFFF
+        r[0] = chk32(r[0] + e * 977)
+        r[1] = chk32(r[1] + e * 8)
+    carry = 0
+    for k in range(8):
+        v = chk32(r[k] + carry)
+        r[k] = v & K_MASK
+        carry = v >> K_B
+    r[8] = chk32(r[8] + carry)
+    assert from_limbs(r, K_B) < (1 << 256) + (1 << 38) and r[8] <= 1 << 24 and all(x <= K_MASK for x in r[:8])
+    plimbs = [(K_P >> (K_B * i)) & K_MASK for i in range(8)] + [K_P >> (K_B * 8)]
+    assert plimbs == [0x1FFFFC2F, 0x1FFFFFF7] + [K_MASK] * 6 + [0xFFFFFF]
+    return all(x == 0 for x in r) or r == plimbs
+
+
 def k256_norm(a):
     """carry-propagate a lazy element (limbs < 2^32) and fold the top: magnitude 1."""
     r = [0] * 9
@@ -559,6 +587,7 @@ def selftest(trials=300, seed=1):
         cases.append([rng.choice([0, 1, K_MASK, K_MASK + 1, K_LB - 1, rng.randrange(K_LB)]) for _ in range(9)])
     for a in cases:
         assert k256_to_words_m1(a) == from_limbs(a, K_B) % K_P
+        assert k256_is_zero_m1(a) == (from_limbs(a, K_B) % K_P == 0)
     # Field::mul_sub / sqr_sub on the Montgomery fields: the subtrahend's limbs ((multiple of p) - c, anything below 2^32) enter
     # the high columns before the rows — products at each set's limit with the largest addends, then random ones; the value must
     # be a b / R + addend and no accumulator may overflow (the chk64 / chk_s64 inside the routines)

@@ -38,6 +38,11 @@ KERNELS = {
     "k_fixed_base_ct<K256Params>": ("ct", "K256Params", "k_fixed_base_ct", 1 << 20, "fixed_k256_ct"),
     "k_var_base_ct<K256Params>": ("ct", "K256Params", "k_var_base_ct", 1 << 20, "lincomb_ct_k256"),
 }
+# what a reader of a kernel's static figures must know (appended to its `source`)
+SOURCE_NOTES = {
+    "k_fixed_base<K256Params>": "; the static mix (isa_top, mad_share, slots_per_inst, static_valu_instructions) is of the WHOLE kernel and "
+                                "includes the cold state-machine loop of the comb walk; the hot loop: profiles/fixed_trim/isa_before_after.txt",
+}
 # per-group compile flags of elliptic-curves_amd/Makefile (FLAGS_<group>: none at present)
 GROUP_FLAGS = {}
 HALF_SLOT_EXCEPT = ("_co_",)          # carry-producing / -consuming VOP2 ops were measured at the full cost
@@ -88,7 +93,7 @@ def main():
             "write_bytes": rec["WRITE_SIZE"] * 1024 if "WRITE_SIZE" in rec else None,
             "gui_cycles": rec.get("GRBM_GUI_ACTIVE"), "sq_busy_cycles": rec.get("SQ_BUSY_CYCLES"),
             "sq_wave_cycles": rec.get("SQ_WAVE_CYCLES"), "waves": rec.get("SQ_WAVES"),
-            "source": rec["_source"] + " + ISA histogram (tools/roofline_consts.py)",
+            "source": rec["_source"] + " + ISA histogram (tools/roofline_consts.py)" + SOURCE_NOTES.get(name, ""),
         }
         print("%-32s insts %.4g  slots/inst %.3f  mad %.3f  fetch %s write %s" % (
             name, out[name]["insts_valu"], h["slots_per_inst"], h["mad_share"], out[name]["fetch_bytes"], out[name]["write_bytes"]))
