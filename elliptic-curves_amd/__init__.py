@@ -69,6 +69,7 @@ ABI_SYMBOLS = [
     "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_sign_msg_batch_dev", "ecgpu_schnorr_sign_raw_batch", "ecgpu_schnorr_sign_raw_batch_dev",
     "ecgpu_hash_to_curve_batch", "ecgpu_encode_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_map_to_curve_batch",
     "ecgpu_sm2_pke_encrypt_batch", "ecgpu_sm2_pke_decrypt_batch",
+    "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -569,6 +570,50 @@ class Engine:
         self._chk(self._lib.ecgpu_sm2dsa_verify_msg_batch(self._ctx, _hp(dd), ctypes.c_size_t(len(distid)), _hp(qq), _hp(mm),
                                                           ctypes.c_size_t(msg_len), _hp(sg), ctypes.c_size_t(n), _hp(ok)))
         return ok
+
+    # ---- SM2DSA signing (sm2): keys and nonces are secrets, as for the ECDSA signing methods below ----
+    def _sm2_sign_out(self, n, out, ok):
+        """out / ok: optional preallocated uint8 arrays (n*64, n) to write into, e.g. from host_alloc or reused from call to call (a
+        fresh array's pages are first touched by the copy that fills it, which costs more than the call)"""
+        out = np.zeros(n * 64, np.uint8) if out is None else out
+        ok = np.zeros(n, np.uint8) if ok is None else ok
+        for a, need in ((out, n * 64), (ok, n)):
+            if a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < need:
+                raise EcgpuError(ERR_ARG, "output buffer must be contiguous uint8 of at least %d bytes" % need)
+        return out, ok
+
+    def sm2dsa_sign(self, d, k, e, out=None, ok=None):
+        """SM2DSA with the caller's nonce (GB/T 32918.2 A3-A7; this form is ours, the reference has none): d, k, e n*32 big-endian
+        bytes each; returns (sig uint8[n*64] = r || s, ok uint8[n])."""
+        dd, kk, ee = _host(d), _host(k), _host(e)
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("k", kk, n * 32); _need("e", ee, n * 32)
+        sig, ok = self._sm2_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_sm2dsa_sign_batch(self._ctx, _hp(dd), _hp(kk), _hp(ee), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
+
+    def sm2dsa_sign_rfc6979(self, d, e, out=None, ok=None):
+        """`PrehashSigner::sign_prehash` (sm2): the one RFC 6979 candidate over HMAC-SM3, generated on the device; d, e n*32 bytes;
+        returns (sig, ok).  An element whose candidate is outside [1, n) gets ok = 0: there is no retry, as in the reference."""
+        dd, ee = _host(d), _host(e)
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("e", ee, n * 32)
+        sig, ok = self._sm2_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_sm2dsa_sign_rfc6979_batch(self._ctx, _hp(dd), _hp(ee), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
+
+    def sm2dsa_sign_msg(self, distid, d, msgs, msg_len, out=None, ok=None):
+        """`SigningKey::new(distid, sk)?.sign(msg)` (sm2): one distinguishing identifier, keys n*32, messages n*msg_len (one length
+        per call, 0 allowed); PA = d G, Z, e = SM3(Z || M) and the nonce are computed on the device; returns (sig, ok)."""
+        ii = _host(distid) if len(distid) else None
+        dd = _host(d)
+        mm = _host(msgs) if msg_len else None
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("msgs", mm, n * msg_len)
+        sig, ok = self._sm2_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_sm2dsa_sign_msg_batch(self._ctx, _hp(ii), ctypes.c_size_t(len(distid)), _hp(dd), _hp(mm),
+                                                        ctypes.c_size_t(msg_len), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
 
     def bign_verify(self, h, sigs, q_xy):
         """Batch bign verification on the prehash (bign256): h = belt-hash(message) as 32 bytes, signatures n*48 (S0 || S1), keys

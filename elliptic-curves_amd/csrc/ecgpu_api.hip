@@ -260,7 +260,7 @@ struct SyncScope {
 // from its secrets — k P in projective form, the running products of the batch inversion, the affine products of an ECDH —
 // is zeroed behind its last kernel (stream-ordered), and `staging` also clears the copies a host-pointer call made of the
 // caller's scalars and results.  The caller's own buffers are the caller's to wipe; ecgpu_wipe does the same on request.
-enum : int { WIPE_SCRATCH = 1, WIPE_EC = 2, WIPE_STAGING = 4, WIPE_SIGN = 8 };
+enum : int { WIPE_SCRATCH = 1, WIPE_EC = 2, WIPE_STAGING = 4, WIPE_SIGN = 8, WIPE_PREHASH = 16 };
 void wipe_bufs(ecgpu_ctx* ctx, std::initializer_list<DevBuf*> bufs) {
     // what has been asked of a buffer since its last wipe, not its capacity: after one 2^20-term batch the scratch holds
     // ~170 MB, and zeroing all of it behind every later 1,024-scalar `_ct` call (or every chunk of a pipelined one) cost tens
@@ -275,6 +275,10 @@ void wipe_scratch(ecgpu_ctx* ctx, int what) {
     if (what & WIPE_EC) wipe_bufs(ctx, {&ctx->ec_xy, &ctx->ec_inf});
     if (what & WIPE_STAGING) wipe_bufs(ctx, {&ctx->in0, &ctx->in3, &ctx->out0, &ctx->out1});
     if (what & WIPE_SIGN) wipe_bufs(ctx, {&ctx->sg_k, &ctx->sg_flag, &ctx->sg_state, &ctx->sg_dp, &ctx->ct_flags});
+    // SM2DSA signing keeps e = SM3(Z || M) in ec_e.  Z hashes PA = d G, a PUBLIC value, so e is no more secret than the z that
+    // ecdsa_sign_dev leaves in the same buffer; it is zeroed all the same because the contract of these calls lists the e buffer
+    // among what is wiped behind them (include/ecgpu.h)
+    if (what & WIPE_PREHASH) wipe_bufs(ctx, {&ctx->ec_e});
 }
 struct CtWipe {
     ecgpu_ctx* ctx;
@@ -754,6 +758,45 @@ int schnorr_sign_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_
     call.mark(1);
     if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
     launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
+    call.mark(2);
+    return call.done();
+}
+
+// SM2DSA signing (ecgpu_sm2sign.h), in the frame of schnorr_sign_dev.  d_k: the caller's nonce (the standard's A3-A7); d_k == nullptr:
+// the ONE candidate of RFC 6979 over HMAC-SM3 (k_sm2_rfc6979; no retry kernel).  from_msg: d_e holds n messages of msg_len bytes and
+// the fixed-base kernel runs twice — PA = d G (affine into ec_xy), e = SM3(Z || M) into ec_e (k_sm2_sign_e), then R = k G.  d_e is
+// otherwise the prehash array.  sg_k, sg_flag, ec_e, projective and affine R are wiped behind the last kernel.  There is no public
+// `_dev` form of these calls yet: the host-pointer entry points have checked every argument before a chunk reaches this function.
+int sm2dsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_e, size_t n, void* d_sig, void* d_ok,
+                    bool from_msg = false, const void* d_distid = nullptr, size_t distid_len = 0, size_t msg_len = 0) {
+    using C = Sm2Params;
+    constexpr int NS = Field<C>::NS;
+    int rc;
+    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN | WIPE_PREHASH,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
+                  {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}, {ctx->ec_e, n * 32 + 16, from_msg}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p;
+    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
+    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
+    call.mark(0);
+    if (from_msg) {
+        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_d, n, k, flag);                 // d, or 1 in place of an unusable key
+        launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+        if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                     // PA = d G
+        launch_sm2_sign_e<C>(ctx->stream, (const uint8_t*)d_distid, distid_len, xy, (const uint8_t*)d_e, msg_len, n, (uint8_t*)ctx->ec_e.p);
+        d_e = ctx->ec_e.p;
+    }
+    if (d_k)
+        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, k, flag);
+    else
+        launch_sm2_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_e, n, k, flag);
+    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    call.mark(1);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
+    launch_sm2dsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, k, flag, (const uint8_t*)d_e, xy, inf, n, (uint8_t*)d_sig, (uint8_t*)d_ok);
     call.mark(2);
     return call.done();
 }
@@ -2663,6 +2706,36 @@ int ecgpu_schnorr_sign_raw_batch(ecgpu_ctx* ctx, const uint8_t* sk, const uint8_
     return staged(ctx, n, {{sk, &ctx->in0, 32, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}, {aux_rand, &ctx->in3, 32, SECRET}},
                   {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
                       return ecgpu_schnorr_sign_raw_batch_dev(ctx, in[0], in[1], msg_len, in[2], m, out[0], out[1]);
+                  });
+}
+
+// ---- SM2DSA signing: keys and nonces are staged as secrets; prehashes, messages and signatures are public ----
+// (host-pointer forms only, like the SM2 encryption calls: sm2dsa_sign_dev is internal, every chunk reaches it through `staged`)
+int ecgpu_sm2dsa_sign_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* k, const uint8_t* e, size_t n, uint8_t* out_sig, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(n && (!d || !k || !e || !out_sig || !ok))) return h.rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {k, &ctx->in3, 32, SECRET}, {e, &ctx->in2, 32}},
+                  {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return sm2dsa_sign_dev(ctx, in[0], in[1], in[2], m, out[0], out[1]);
+                  });
+}
+
+int ecgpu_sm2dsa_sign_rfc6979_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* e, size_t n, uint8_t* out_sig, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(n && (!d || !e || !out_sig || !ok))) return h.rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {e, &ctx->in2, 32}}, {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return sm2dsa_sign_dev(ctx, in[0], nullptr, in[1], m, out[0], out[1]); });
+}
+
+int ecgpu_sm2dsa_sign_msg_batch(ecgpu_ctx* ctx, const uint8_t* distid, size_t distid_len, const uint8_t* d, const uint8_t* msgs,
+                                size_t msg_len, size_t n, uint8_t* out_sig, uint8_t* ok) {
+    HostCall h(ctx, __func__, ECGPU_SM2);
+    if (h.bad(distid_len > 8191 || (distid_len && !distid) || (n && (!d || !out_sig || !ok || (msg_len && !msgs))))) return h.rc;
+    int rc = upload(ctx, ctx->ec_id, distid, distid_len);          // one identifier for the whole batch: not an array of the list
+    if (rc != ECGPU_OK) return rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}},
+                  {{out_sig, &ctx->out0, 64}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return sm2dsa_sign_dev(ctx, in[0], nullptr, in[1], m, out[0], out[1], true, ctx->ec_id.p, distid_len, msg_len);
                   });
 }
 

@@ -2,6 +2,7 @@
 // that tools/ct_isa_check.py --unit sign can look at exactly these kernels, and so that the HMAC bodies build beside the rest
 #include "ecgpu_sign.h"
 #include "ecgpu_pke.h"
+#include "ecgpu_sm2sign.h"
 #include "ecgpu_launch.h"
 
 namespace ecgpu {
@@ -47,6 +48,25 @@ void pke_open_impl(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, cons
     if constexpr (C::ID == CURVE_SM2)
         hipLaunchKernelGGL(k_pke_open<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, x2y2, flag, c2, msg_len, c3, n, msgs_out, ok);
 }
+
+// SM2DSA signing exists over the sm2 curve with SM3 only (ecgpu_sm2sign.h): the other curves' translation units hold none of its
+// kernels
+template <class C>
+void sm2_sign_e_impl(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* pa_xy, const uint8_t* msgs, size_t msg_len,
+                     size_t n, uint8_t* e_out) {
+    if constexpr (Sm2Sign<C>::value)
+        hipLaunchKernelGGL(k_sm2_sign_e<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, distid, distid_len, pa_xy, msgs, msg_len, n, e_out);
+}
+template <class C>
+void sm2_rfc6979_impl(hipStream_t s, const uint8_t* d, const uint8_t* e, size_t n, uint8_t* k_out, uint8_t* flag) {
+    if constexpr (Sm2Sign<C>::value) hipLaunchKernelGGL(k_sm2_rfc6979<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, e, n, k_out, flag);
+}
+template <class C>
+void sm2dsa_sign_finish_impl(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* e,
+                             const uint8_t* r_xy, const uint8_t* r_inf, size_t n, uint8_t* sig, uint8_t* ok) {
+    if constexpr (Sm2Sign<C>::value)
+        hipLaunchKernelGGL(k_sm2dsa_sign_finish<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, k, k_flag, e, r_xy, r_inf, n, sig, ok);
+}
 }  // namespace
 
 template <> void launch_sign_nonce_load<CurveT>(hipStream_t s, const uint8_t* k_in, size_t n, uint8_t* k_out, uint8_t* flag) {
@@ -89,6 +109,18 @@ template <> void launch_pke_seal<CurveT>(hipStream_t s, const uint8_t* x2y2, con
 template <> void launch_pke_open<CurveT>(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* c2, size_t msg_len,
                                          const uint8_t* c3, size_t n, uint8_t* msgs_out, uint8_t* ok) {
     pke_open_impl<CurveT>(s, x2y2, flag, c2, msg_len, c3, n, msgs_out, ok);
+}
+template <> void launch_sm2_sign_e<CurveT>(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* pa_xy,
+                                          const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* e_out) {
+    sm2_sign_e_impl<CurveT>(s, distid, distid_len, pa_xy, msgs, msg_len, n, e_out);
+}
+template <> void launch_sm2_rfc6979<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* e, size_t n, uint8_t* k_out, uint8_t* flag) {
+    sm2_rfc6979_impl<CurveT>(s, d, e, n, k_out, flag);
+}
+template <> void launch_sm2dsa_sign_finish<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag,
+                                                   const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf, size_t n, uint8_t* sig,
+                                                   uint8_t* ok) {
+    sm2dsa_sign_finish_impl<CurveT>(s, d, k, k_flag, e, r_xy, r_inf, n, sig, ok);
 }
 
 }  // namespace ecgpu

@@ -134,6 +134,13 @@ template <class C> void launch_pke_seal(hipStream_t s, const uint8_t* x2y2, cons
                                         uint8_t* c1, uint8_t* c2, uint8_t* c3, uint8_t* ok);
 template <class C> void launch_pke_open(hipStream_t s, const uint8_t* x2y2, const uint8_t* flag, const uint8_t* c2, size_t msg_len,
                                         const uint8_t* c3, size_t n, uint8_t* msgs_out, uint8_t* ok);
+// SM2DSA signing (ecgpu_sm2sign.h; launches nothing for a curve other than sm2).  sign_e: e = SM3(Z || M) from the affine PA = d G;
+// rfc6979: the ONE candidate of the HMAC-SM3 generator (1 in place of a rejected one) and its verdict; finish: r || s and ok
+template <class C> void launch_sm2_sign_e(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* pa_xy, const uint8_t* msgs,
+                                          size_t msg_len, size_t n, uint8_t* e_out);
+template <class C> void launch_sm2_rfc6979(hipStream_t s, const uint8_t* d, const uint8_t* e, size_t n, uint8_t* k_out, uint8_t* flag);
+template <class C> void launch_sm2dsa_sign_finish(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* e,
+                                                  const uint8_t* r_xy, const uint8_t* r_inf, size_t n, uint8_t* sig, uint8_t* ok);
 
 // ---- group "h2c": RFC 9380 hash-to-curve (ecgpu_h2c.h); k256, p256 and p384 only (h2c_supported), nothing is launched for the others ----
 template <class C> bool h2c_supported();

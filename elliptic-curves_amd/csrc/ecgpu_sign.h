@@ -103,9 +103,10 @@ struct SignHash {
 // inlined once per kernel.  Which blocks a step has depends on `kind`, which is a loop counter, never on data.
 enum : int { DRBG_K_LONG = 0, DRBG_K_SHORT = 1, DRBG_V = 2 };
 
-template <class C, int D = EcdsaDigest<C>::value>
+// HT: the hash as the HMAC sees it (SignHash<D>; SignHashSm3 of ecgpu_sm2sign.h for SM2DSA, whose digest is D = 32 bytes too)
+template <class C, int D = EcdsaDigest<C>::value, class HT = SignHash<D>>
 struct Rfc6979 {
-    using H = SignHash<D>;
+    using H = HT;
     using W = typename H::W;
     ECGPU_CONST int N = C::N, L = WireBytes<C>::value, HW = H::HW, BB = H::BB, WB = H::WB;
     ECGPU_CONST int NV = (L + D - 1) / D;                // HMAC outputs per candidate: 2 for p521 (64 < 66), else 1

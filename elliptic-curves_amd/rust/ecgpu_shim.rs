@@ -586,6 +586,45 @@ pub mod gpu {
         Some(sig.chunks(64).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
     }
 
+    /// Batch form of `PrehashSigner::sign_prehash` of `sm2::dsa::SigningKey` (sm2/src/dsa/signing.rs:122-126, 213-258): `prehashes`
+    /// are exactly 32 bytes each (`bytes2scalar`).  The one RFC 6979 candidate over HMAC-SM3, R = k G on the uniform-schedule kernel
+    /// and s = (1 + d)^-1 (k - r d) are computed on the device (`ecgpu_sm2dsa_sign_rfc6979_batch`); the wire copy of the keys is
+    /// wiped here, the device side by the library.  `None` per element where the reference returns `Err` (a candidate >= n,
+    /// r = 0, r + k = 0, d = n - 1, s = 0).  The signature is r || s; there is no recovery id.
+    pub fn sm2dsa_sign_prehash_batch(keys: &[NonZeroScalar<sm2::Sm2>], prehashes: &[[u8; 32]]) -> Option<Vec<Option<[u8; 64]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = keys.len();
+        assert!(prehashes.len() == n);
+        let mut d = Zeroizing::new(Vec::with_capacity(32 * n));
+        for k in keys {
+            d.extend_from_slice(&k.to_repr());
+        }
+        let (mut sig, mut ok) = (vec![0u8; 64 * n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_sm2dsa_sign_rfc6979_batch(eng.0, d.as_ptr(), prehashes.as_ptr() as *const u8, n, sig.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sig.chunks(64).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
+    }
+
+    /// Batch form of `SigningKey::new(distid, sk)?.sign(msg)` (sm2/src/dsa/signing.rs:81-88, 162-174) for signers that share one
+    /// distinguishing identifier and messages of one length: PA = d G, Z = `hash_z(distid, PA)`, e = SM3(Z || M) and the RFC 6979
+    /// form above all run on the device (`ecgpu_sm2dsa_sign_msg_batch`).
+    pub fn sm2dsa_sign_batch(distid: &[u8], keys: &[NonZeroScalar<sm2::Sm2>], msgs: &[u8], msg_len: usize) -> Option<Vec<Option<[u8; 64]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = keys.len();
+        assert!(msgs.len() == n * msg_len && distid.len() <= 8191);
+        let mut d = Zeroizing::new(Vec::with_capacity(32 * n));
+        for k in keys {
+            d.extend_from_slice(&k.to_repr());
+        }
+        let (mut sig, mut ok) = (vec![0u8; 64 * n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_sm2dsa_sign_msg_batch(eng.0, distid.as_ptr(), distid.len(), d.as_ptr(), msgs.as_ptr(), msg_len, n, sig.as_mut_ptr(),
+                                        ok.as_mut_ptr())
+        })?;
+        Some(sig.chunks(64).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
+    }
+
     /// Batch form of `hash2curve::GroupDigest::hash_from_bytes(&[msg], &[dst])` (hash2curve/src/group_digest.rs) for the curves
     /// with a suite on the device (k256, p256, p384): `msgs` holds `n` messages of `msg_len` bytes each, `dst` is the one domain
     /// separation tag of the batch (not empty: `Domain::xmd` refuses that, and so does the library).
@@ -816,6 +855,17 @@ pub mod gpu {
 //
 //     and `ecgpu::gpu::sm2_pke_decrypt_batch(&keys, mode, &ciphers)` for a server that decrypts for many keys.  The nonce loop,
 //     the `Mode` byte order and the SEC1 tag stay on the Rust side; (x2, y2) stays on the device.
+//
+// (3b) sm2/src/dsa/signing.rs:122-126,162-174 — beside `PrehashSigner::sign_prehash` and `Signer::try_sign`, batch functions over
+//     many keys:
+//
+//         #[cfg(feature = "gpu")]
+//         pub fn sign_prehash_batch(keys: &[SigningKey], prehashes: &[[u8; 32]]) -> Vec<Result<Signature>>
+//         #[cfg(feature = "gpu")]
+//         pub fn sign_batch(distid: &str, keys: &[SigningKey], msgs: &[u8], msg_len: usize) -> Vec<Result<Signature>>
+//
+//     on `ecgpu::gpu::sm2dsa_sign_prehash_batch` resp. `ecgpu::gpu::sm2dsa_sign_batch` (fallback: the per-key calls).  One
+//     candidate of the generator and no retry, as `sign_prehash_rfc6979` has it; `RandomizedPrehashSigner` stays on the CPU.
 //
 // (4) primeorder curves select their generator-multiplication backend through `PrimeCurveParams::Backend`
 //     (primeorder/src/lib.rs:62; p256/src/arithmetic/tables.rs:24-44).  `GpuBackend` below is such a backend: single calls

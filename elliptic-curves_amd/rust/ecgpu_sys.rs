@@ -669,6 +669,34 @@ unsafe extern "C" {
         d_out_sig: *mut c_void,
         d_ok: *mut c_void,
     ) -> c_int;
+    pub fn ecgpu_sm2dsa_sign_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        k: *const u8,
+        e: *const u8,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_sm2dsa_sign_rfc6979_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        e: *const u8,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_sm2dsa_sign_msg_batch(
+        ctx: *mut EcgpuCtx,
+        distid: *const u8,
+        distid_len: usize,
+        d: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_batch_mul_ct_xyz(
         ctx: *mut EcgpuCtx,
         curve: c_int,

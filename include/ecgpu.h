@@ -603,6 +603,41 @@ int ecgpu_schnorr_sign_raw_batch(ecgpu_ctx *ctx, const uint8_t *sk, const uint8_
 int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx *ctx, const void *d_sk, const void *d_msgs, size_t msg_len,
                                      const void *d_aux_rand, size_t n, void *d_out_sig, void *d_ok);
 
+/* ---- batch SM2DSA signing (GB/T 32918.2 section 6.1): the signing half of `sm2::dsa` ---------------------------------------
+ * The sm2 parameter set only, hence no `curve` argument (as for ecgpu_sm2dsa_verify_batch).  Everything the block above says
+ * about the ECDSA calls holds here: R = k G (and PA = d G of the message form) is the kernel of ecgpu_batch_mul_base_ct; in the
+ * kernels around it no branch and no address depends on d, k, e or anything derived from them
+ * (tools/ct_isa_check.py --unit sm2sign; tests/test_sm2sign_isa.py); (1 + d)^-1 is one branch-free division-step inversion per
+ * element; everything derived from d or k on the device (the nonces and their verdicts, e, projective and affine R, the staged
+ * copies of d and k) is zeroed behind the last kernel in stream order, and ecgpu_wipe covers the same buffers.  An element that cannot be
+ * signed never fails the batch: it gets a zero record and ok[i] = 0, and its neighbours are untouched.
+ *     e = prehash mod n (`bytes2scalar`; exactly 32 bytes),  R = k G,  r = e + x(R) mod n,  s = (1 + d)^-1 (k - r d) mod n
+ * out_sig: n*64 bytes r || s, big-endian.  There is no low-S rule and no recovery id.
+ *
+ * ecgpu_sm2dsa_sign_batch — the standard's steps A3-A7 with the caller's nonce.  THIS FORM IS OURS: the reference has no entry
+ *   point that takes a nonce; it exists for callers with their own RNG and for the standard's known answer (GB/T 32918.5-2017
+ *   Annex A).  d, k, e: n*32 bytes each.  ok[i] = 1 iff 1 <= d < n, d != n - 1 (1 + d has no inverse), 1 <= k < n, r != 0,
+ *   r + k != 0 mod n and s != 0.
+ * ecgpu_sm2dsa_sign_rfc6979_batch — `PrehashSigner::sign_prehash` (sm2/src/dsa/signing.rs:122-126, 213-258): the nonce of
+ *   RFC 6979 section 3.2 over HMAC-SM3, x = d as 32 bytes, h1 = (e mod n) as 32 bytes, no additional data.  ONE candidate and no
+ *   retry kernel: this follows the reference's single `fill_next_k` (its source carries a TODO for the loop) — a candidate
+ *   outside [1, n) gives ok[i] = 0 and a zero record, where the ECDSA form above would try the next one.  One difference from
+ *   the reference: k = 0 is refused here, the reference's `from_repr` would accept it (probability 2^-256).
+ * ecgpu_sm2dsa_sign_msg_batch — `SigningKey::new(distid, sk)?.sign(msg)` (:81-88, 162-174): PA = d G, Z = SM3(ENTL || ID || a ||
+ *   b || xG || yG || xA || yA) and e = SM3(Z || M) on the device, then the RFC 6979 form.  distid: distid_len <= 8191 bytes, one
+ *   identifier per call (ECGPU_ERR_ARG above that); msgs: n*msg_len bytes, one uniform length per call, 0 allowed — the argument
+ *   rules of ecgpu_sm2dsa_verify_msg_batch.
+ * Out of scope: `RandomizedPrehashSigner` (32 bytes of additional data make the generator's HMAC message three blocks) and bign
+ * signing (its nonce is belt-based).
+ * Host-pointer forms only, like the SM2 encryption calls below: there is no public `_dev` name yet (every chunk of a call reaches
+ * the internal device-pointer pipeline through the staging path, from 2^19 elements on piece by piece under the transfers).  On
+ * an asynchronous context a call first waits for the queued work and runs synchronously, as every host-pointer call does. */
+int ecgpu_sm2dsa_sign_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *k, const uint8_t *e, size_t n, uint8_t *out_sig,
+                            uint8_t *ok);
+int ecgpu_sm2dsa_sign_rfc6979_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *e, size_t n, uint8_t *out_sig, uint8_t *ok);
+int ecgpu_sm2dsa_sign_msg_batch(ecgpu_ctx *ctx, const uint8_t *distid, size_t distid_len, const uint8_t *d, const uint8_t *msgs,
+                                size_t msg_len, size_t n, uint8_t *out_sig, uint8_t *ok);
+
 /* The same two with projective points: point i is the record X || Y || Z of the wire format above (3L bytes, no flag array),
  * as the reference's `Mul<Scalar>` and `lincomb` take a `ProjectivePoint`.  For every input the results and the return code
  * are those of `to_affine` applied to each record followed by ecgpu_batch_mul_ct / ecgpu_lincomb_ct: X, Y or Z >= p, and a

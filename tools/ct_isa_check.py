@@ -16,6 +16,9 @@ the SM2 public-key encryption kernels (csrc/ecgpu_pke.h, translation unit ecgpu_
 x2 || y2, the keystream, the message bytes and the C3 comparison are all loaded records or derived from them; msg_len and n are
 kernel arguments.  k_pke_load is the SCALAR half of the load step and passes as a whole; the public point (P_B, or the C1 of an
 untrusted ciphertext) is checked by k_pke_point, a kernel of its own that branches on the point on purpose and is not on the list.
+    python tools/ct_isa_check.py --unit sm2sign --curve Sm2Params [--kernels ...]
+the SM2DSA signing kernels (csrc/ecgpu_sm2sign.h, translation unit ecgpu_inst_sign.hip; sm2 only): d, k, e, the affine PA and R,
+the HMAC-SM3 state and the candidate are all loaded records or derived from them; distid_len, msg_len and n are kernel arguments.
 
 How: the translation unit is compiled to assembly (hipcc -S --offload-device-only; no GPU needed) and every selected kernel
 goes through a forward taint analysis over its control-flow graph (register-precise, iterated to a fixed point):
@@ -380,6 +383,7 @@ UNITS = {
     "sign": ("ecgpu_inst_sign.hip", "k_rfc6979_first,k_schnorr_nonce,k_ecdsa_sign_finish,k_schnorr_sign_finish,k_sign_nonce_load"),
     "h2c": ("ecgpu_inst_h2c.hip", "k_h2c_expand,k_h2c_map"),
     "pke": ("ecgpu_inst_sign.hip", "k_pke_load,k_pke_seal,k_pke_open"),
+    "sm2sign": ("ecgpu_inst_sign.hip", "k_sm2_sign_e,k_sm2_rfc6979,k_sm2dsa_sign_finish"),
 }
 
 
@@ -412,7 +416,7 @@ def check(asm, wanted, verbose=False, seen_names=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="append")
-    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, or the SM2 encryption kernels")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, the SM2 encryption kernels, or the SM2DSA signing kernels")
     ap.add_argument("--kernels", help="default: the data-independent kernels of the unit")
     ap.add_argument("--must-flag", default="", help="kernels of the unit that must be reported (comma-separated)")
     ap.add_argument("--asm", help="check an existing .s file instead of compiling")

@@ -2,9 +2,11 @@
 """Randomised differential run on the GPU box: random parameter set (all twelve), sizes, window widths, chunk sizes, sort
 modes, scalar split (GLV / plain), duplicated / cancelling / identity terms, random shard splits through the parts / finish
 halves; every result against the oracle (n <= 2^13) or a group identity (larger n).  One-off evidence, not part of the test
-suite:    FUZZ_SECONDS=200 FUZZ_SEED=1 python tools/gpu_fuzz.py"""
+suite:    FUZZ_SECONDS=200 FUZZ_SEED=1 python tools/gpu_fuzz.py
+FUZZ_KINDS=sm2sign (a comma-separated list of case kinds) restricts the run to those kinds, each on a parameter set that has it."""
 import importlib
 import collections
+import hashlib
 import os
 import random
 import sys
@@ -25,6 +27,9 @@ e = ec.Engine(0, variant="knobs")   # the tool build: the ECGPU_* knobs below ar
 rng = random.Random(int(os.environ.get("FUZZ_SEED", "20260924")))
 budget = float(os.environ.get("FUZZ_SECONDS", "150"))
 t_end = time.time() + budget
+KINDS = ["msm", "msm", "msm", "shards", "shard_lanes", "fixed", "var", "sig", "lanes"]
+ONLY = [k for k in os.environ.get("FUZZ_KINDS", "").split(",") if k]
+KIND_SETS = {"sm2sign": ["sm2"], "bign": ["bign256"]}        # kinds that exist on one parameter set only
 stats = collections.defaultdict(int)
 NAMES = ["k256", "p256", "p384", "sm2", "p224", "p192", "p521", "bp256", "bp384", "bp256t1", "bp384t1", "bign256"]
 DEFAULT_W = {"k256": 26, "p256": 24, "p384": 20, "sm2": 24, "p224": 24, "p192": 24, "p521": 20, "bp256": 24, "bp384": 20,
@@ -71,13 +76,48 @@ def note(exc_type, exc, tb):
 sys.excepthook = note
 kind = c = n = None
 while time.time() < t_end:
-    c = pyec.CURVES[rng.choice(NAMES)]
+    if ONLY:
+        kind = rng.choice(ONLY)
+        c = pyec.CURVES[rng.choice(KIND_SETS.get(kind, NAMES))]
+    else:                                                    # (the order of the two draws is the one recorded seeds were run with)
+        c = pyec.CURVES[rng.choice(NAMES)]
+        kind = rng.choice(KINDS)
     L = c.L
-    kind = rng.choice(["msm", "msm", "msm", "shards", "shard_lanes", "fixed", "var", "sig", "lanes"])
     if kind == "sig" and c.name == "bign256":
         kind = "bign"
     if kind == "sig" and c.name == "sm2":
-        kind = "var"
+        kind = "sm2sign"
+    if kind == "sm2sign":
+        # SM2DSA: random keys (a few unusable), random identifier and message lengths; what the device signs, the device and the
+        # oracle verify under PA = d G, a disturbed signature is refused, and the prehash form of the same e gives the same bytes
+        n = rng.randrange(1, 600)
+        ds = bytearray(rand_scalars(c.cid, n, rng.randrange(1 << 30)))
+        dead = set()
+        for _ in range(rng.randrange(0, 3)):
+            i = rng.randrange(n)
+            ds[32 * i:32 * i + 32] = rng.choice([0, c.n - 1, c.n, (1 << 256) - 1]).to_bytes(32, "big")
+            dead.add(i)
+        ds = bytes(ds)
+        distid = bytes(rng.randrange(256) for _ in range(rng.choice([0, 1, 16, 53, 54, 62, 200])))
+        msg_len = rng.choice([0, 1, 23, 24, 32, 33, 88, 200])
+        msgs = bytes(rng.randrange(256) for _ in range(n * msg_len))
+        sig, ok = e.sm2dsa_sign_msg(distid, ds, msgs, msg_len)
+        assert [i for i in range(n) if not ok[i]] == sorted(dead), ("sm2sign ok", n, sorted(dead))
+        one = (1).to_bytes(32, "big")
+        Q = bytes(e.mul_by_generator(c.cid, b"".join(one if i in dead else ds[32 * i:32 * i + 32] for i in range(n)))[0])
+        want = bytes(0 if i in dead else 1 for i in range(n))
+        assert bytes(e.sm2dsa_verify_msg(distid, Q, msgs, msg_len, sig)) == want, ("sm2sign verify", n, msg_len, len(distid))
+        assert bytes(oracle_lib.sm2dsa_verify_msg(distid, Q, msgs, msg_len, sig)) == want, ("sm2sign oracle", n, msg_len, len(distid))
+        bad = bytearray(bytes(sig))
+        j = rng.randrange(n)
+        bad[64 * j + rng.randrange(64)] ^= 1 << rng.randrange(8)
+        assert not e.sm2dsa_verify_msg(distid, Q, msgs, msg_len, bytes(bad))[j], ("sm2sign disturbed", n, j)
+        es = b"".join(hashlib.new("sm3", pyec.sm2_za(c, distid, pyec.dec_point(c, Q[64 * i:64 * i + 64], 0)) +
+                                  msgs[i * msg_len:(i + 1) * msg_len]).digest() for i in range(min(n, 40)))
+        sig2, ok2 = e.sm2dsa_sign_rfc6979(ds[:32 * min(n, 40)], es)
+        assert bytes(sig2) == bytes(sig[:64 * min(n, 40)]) and bytes(ok2) == bytes(ok[:min(n, 40)]), ("sm2sign prehash", n)
+        stats["sm2sign"] += 1
+        continue
     if kind == "msm":
         big = rng.random() < 0.25
         n = rng.randrange(1 << 14, 1 << 19) if big else rng.randrange(1, 1 << 13)

@@ -12,6 +12,11 @@ much as inputs can.
                                                 tracing alongside): the counters of k_sign_nonce_load, k_rfc6979_first,
                                                 k_ecdsa_sign_finish, k_schnorr_nonce, k_schnorr_sign_finish and k_fixed_base_ct must be
                                                 IDENTICAL across the classes zeros / ones / random / n - 1 / invalid (0xff bytes)
+    python tools/gpu_sign_rates.py --sm2        SM2DSA signing (ecgpu_sm2dsa_sign_batch / _sign_rfc6979_batch / _sign_msg_batch): the rates part and
+                                                the trace part for the three forms on sm2, beside sm2's ecgpu_batch_mul_base_ct of the
+                                                same run (profiles/sm2sign/rates.txt).  These calls have host-pointer forms only: their
+                                                wall time includes the PCIe staging, and so does the yardstick's (its host-pointer
+                                                form), which is timed again with reused and with page-locked arrays
     python tools/gpu_sign_rates.py --child FORM CURVE CLASS LOG2N     (internal) one call
 
 Every part after the first starts GPU processes of its own.  The first child that does not exit with status 0 ends the whole
@@ -20,6 +25,7 @@ script there (ChildFailed): its exit status and the end of its output are printe
 import csv
 import glob
 import os
+import statistics
 import subprocess
 import sys
 import time
@@ -33,6 +39,9 @@ import importlib  # noqa: E402
 
 CURVES = {"k256": 0, "p256": 1}
 FORMS = ("sign", "rfc6979", "msg", "schnorr")
+SM2_CURVES = {"sm2": 3}
+SM2_FORMS = ("sm2_sign", "sm2_rfc6979", "sm2_msg")
+SM2_DISTID = b"1234567812345678"
 CLASSES = ("zeros", "ones", "random", "nm1", "invalid")
 CT_KERNELS = ("k_sign_nonce_load", "k_rfc6979_first", "k_ecdsa_sign_finish", "k_schnorr_nonce", "k_schnorr_sign_finish",
               "k_fixed_base_ct")
@@ -116,14 +125,89 @@ def rates():
     eng.close()
 
 
+class Sm2Host:
+    """The SM2DSA signing forms and their yardstick on 2^lg elements in host memory: these calls have host-pointer forms only, so
+    a call is its staging and its kernels together.  Nothing is built that the forms do not use."""
+
+    def __init__(self, ecgpu, eng, n, cls="random"):
+        self.eng, self.n = eng, n
+        self.d, self.k, self.e = (class_bytes(ecgpu, SM2_CURVES["sm2"], n, cls, seed) for seed in (0x5161, 0x5162, 0x5163))
+        self.msgs = class_bytes(ecgpu, SM2_CURVES["sm2"], n, cls, 0x5164, MSG_LEN)
+        # the output arrays are made (and touched) once and reused: a fresh numpy array's pages are first touched by the copy that
+        # fills it, which takes several times as long as the whole call (the probe at the end of sm2_rates measures it)
+        self.xy, self.inf, self.sig, self.ok = (np.zeros(n * w, np.uint8) for w in (64, 1, 64, 1))
+        self.calls = {
+            "ecgpu_batch_mul_base_ct (sm2)": lambda: eng.mul_by_generator(SM2_CURVES["sm2"], self.d, out=self.xy, inf=self.inf, constant_time=True),
+            "sm2_sign": lambda: eng.sm2dsa_sign(self.d, self.k, self.e, out=self.sig, ok=self.ok),
+            "sm2_rfc6979": lambda: eng.sm2dsa_sign_rfc6979(self.d, self.e, out=self.sig, ok=self.ok),
+            "sm2_msg": lambda: eng.sm2dsa_sign_msg(SM2_DISTID, self.d, self.msgs, MSG_LEN, out=self.sig, ok=self.ok),
+        }
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    out = fn()                                             # (a host-pointer call returns after its last copy has arrived)
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def sm2_rates(rounds=5):
+    """the four host-pointer calls alternating inside a round, median (min .. max) over the rounds after a warm-up round; then the
+    yardstick again with its output arrays reused and with page-locked arrays: what of its wall time is the host side of the staging"""
+    ecgpu, eng = engine()
+    n, sm2 = 1 << 20, SM2_CURVES["sm2"]
+    h = Sm2Host(ecgpu, eng, n)
+    print("SM2DSA signing, 2^20 elements in pageable host memory (host-pointer calls: PCIe staging included, there is no other form),")
+    print("one process, the output arrays reused from call to call;")
+    print("median of %d rounds after one warm-up round, the calls alternating inside a round; ms per call (min .. max)" % rounds)
+    times = {name: [] for name in h.calls}
+    signed = {}
+    for rnd in range(rounds + 1):
+        for name, fn in h.calls.items():
+            ms, out = timed(fn)
+            if rnd:
+                times[name].append(ms)
+            if name.startswith("sm2_"):
+                signed[name] = int(out[1].sum())
+    for name, v in times.items():
+        med = statistics.median(v)
+        print("  %-32s %9.2f ms  (%8.2f .. %8.2f)   %6.2f M/s%s" % (name, med, min(v), max(v), n / med / 1e3,
+                                                                   ", %d signed" % signed[name] if name in signed else ""), flush=True)
+    # the staging of the yardstick three ways: fresh output arrays every call (what the Engine methods do when they are given
+    # none), the same two arrays every call (as above), page-locked input and output arrays
+    out, inf = h.xy, h.inf
+    pin_d, pin_out, pin_inf = eng.host_alloc(n * 32), eng.host_alloc(n * 64), eng.host_alloc(n)
+    pin_d[:] = h.d
+    probes = {
+        "fresh pageable outputs": lambda: eng.mul_by_generator(sm2, h.d, constant_time=True),
+        "reused pageable outputs": lambda: eng.mul_by_generator(sm2, h.d, out=out, inf=inf, constant_time=True),
+        "page-locked input and outputs": lambda: eng.mul_by_generator(sm2, pin_d, out=pin_out, inf=pin_inf, constant_time=True),
+    }
+    ptimes = {name: [] for name in probes}
+    for rnd in range(rounds + 1):
+        for name, fn in probes.items():
+            ms, _ = timed(fn)
+            if rnd:
+                ptimes[name].append(ms)
+    print("the yardstick's staging, same process (ecgpu_batch_mul_base_ct on sm2, host-pointer form; 32 MB up, 65 MB down):")
+    for name, v in ptimes.items():
+        print("  %-32s %9.2f ms  (%8.2f .. %8.2f)" % (name, statistics.median(v), min(v), max(v)), flush=True)
+    for a in (pin_d, pin_out, pin_inf):
+        eng.host_free(a)
+    eng.close()
+
+
 def child(form, curve, cls, lg):
     """form "all": every form of the curve once (the counter runs); otherwise the one form twice (the second call is the warm one)"""
     ecgpu, eng = engine()
-    cid = CURVES[curve]
+    cid = dict(CURVES, **SM2_CURVES)[curve]
     if form == "all":
         for f in FORMS:
             if f != "schnorr" or cid == 0:
                 Call(ecgpu, eng, f, cid, 1 << lg, cls).run()
+    elif form in SM2_FORMS:
+        h = Sm2Host(ecgpu, eng, 1 << lg, cls)
+        h.calls[form]()
+        h.calls[form]()
     else:
         call = Call(ecgpu, eng, form, cid, 1 << lg, cls)
         call.run()
@@ -150,10 +234,10 @@ def short(kernel):
     return kernel.split("(")[0].replace("void ", "").replace("ecgpu::", "")
 
 
-def trace():
+def trace(curves=CURVES, forms=FORMS):
     print("\nkernels of one call at 2^20 (second of two calls in a process of its own, rocprofv3 --kernel-trace --stats):")
-    for curve in CURVES:
-        for form in FORMS:
+    for curve in curves:
+        for form in forms:
             if form == "schnorr" and curve != "k256":
                 continue
             out = "/tmp/sign_trace_%s_%s" % (curve, form)
@@ -217,9 +301,12 @@ def pmc():
 def main():
     if len(sys.argv) > 5 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5]))
-    parts = [a for a in sys.argv[1:] if a in ("--rates", "--trace", "--pmc")] or ["--rates", "--trace", "--pmc"]
+    parts = [a for a in sys.argv[1:] if a in ("--rates", "--trace", "--pmc", "--sm2")] or ["--rates", "--trace", "--pmc"]
     bad = 0
     try:
+        if "--sm2" in parts:
+            sm2_rates()
+            trace(SM2_CURVES, SM2_FORMS)
         if "--rates" in parts:
             rates()                      # (in this process: an exception or a fault here ends the script by itself)
         if "--trace" in parts:
