@@ -69,7 +69,7 @@ ABI_SYMBOLS = [
     "ecgpu_ecdsa_sign_msg_batch", "ecgpu_ecdsa_sign_msg_batch_dev", "ecgpu_schnorr_sign_raw_batch", "ecgpu_schnorr_sign_raw_batch_dev",
     "ecgpu_hash_to_curve_batch", "ecgpu_encode_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_map_to_curve_batch",
     "ecgpu_sm2_pke_encrypt_batch", "ecgpu_sm2_pke_decrypt_batch",
-    "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch",
+    "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch", "ecgpu_selftest_sign_finish",
 ]
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -878,6 +878,22 @@ class Engine:
         self._chk(self._lib.ecgpu_selftest_point_raw(self._ctx, curve, int(op), _hp(P.view(np.uint8)), _hp(None if Q is None else Q.view(np.uint8)),
                                                      ctypes.c_size_t(n), _hp(out.view(np.uint8))))
         return out.reshape(n, rec)
+
+    def selftest_sign_finish(self, curve, scheme, d, k, flag, z, r_xy, r_inf, msgs=None, msg_len=0, normalize_s=False):
+        """The finish kernels of the signing pipelines on stages the caller supplies (test infrastructure).  scheme 0: ECDSA
+        (k_ecdsa_sign_finish) -> (sig, recid, ok); 1: SM2DSA, z = e -> (sig, ok); 2: BIP340, d = d' || x(P) records of 64 bytes,
+        z unused -> (sig, ok).  flag, r_xy, r_inf: what the nonce, fixed-base and normalisation kernels would have written."""
+        L = _field_bytes(curve)
+        K, F, R, RI = _host(k), _host(flag), _host(r_xy), _host(r_inf)
+        D, Z, M = _host(d), _host(z), _host(msgs)
+        n = K.size // L
+        _need("d", D, n * (2 * L if scheme == 2 else L)); _need("k", K, n * L); _need("flag", F, n); _need("r_xy", R, n * 2 * L)
+        _need("r_inf", RI, n); _need("z", Z, n * L); _need("msgs", M, n * msg_len)
+        sig, recid, ok = np.zeros(n * 2 * L, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self._chk(self._lib.ecgpu_selftest_sign_finish(self._ctx, curve, int(scheme), _hp(D), _hp(K), _hp(F), _hp(Z), _hp(R), _hp(RI), _hp(M),
+                                                       ctypes.c_size_t(msg_len), ctypes.c_size_t(n), int(bool(normalize_s)), _hp(sig),
+                                                       _hp(recid), _hp(ok)))
+        return (sig, recid, ok) if scheme == 0 else (sig, ok)
 
     # ---- device-resident operations (torch uint8 CUDA tensors or raw device pointers) ----
     def mul_by_generator_dev(self, curve, d_scalars, n, d_out_xy, d_out_inf=None, constant_time=False):

@@ -2911,6 +2911,46 @@ int ecgpu_selftest_point_raw(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p
     }, STAGE_WHOLE);
 }
 
+// The signing pipelines' finish kernels on stages the caller supplies (test infrastructure: tests/sign_vectors.py).  Nothing is
+// computed before the kernel: flag, affine R and r_inf are what the nonce, fixed-base and normalisation kernels would have left.
+int ecgpu_selftest_sign_finish(ecgpu_ctx* ctx, int curve, int scheme, const uint8_t* d, const uint8_t* k, const uint8_t* flag,
+                               const uint8_t* z, const uint8_t* r_xy, const uint8_t* r_inf, const uint8_t* msgs, size_t msg_len, size_t n,
+                               int normalize_s, uint8_t* out_sig, uint8_t* out_recid, uint8_t* ok) {
+    HostCall h(ctx, __func__, curve);
+    if (h.rc != ECGPU_OK) return h.rc;
+    const bool ecdsa = scheme == 0, sm2 = scheme == 1, schnorr = scheme == 2;
+    if (!(ecdsa || sm2 || schnorr)) return arg_error(ctx, __func__);
+    if ((ecdsa && not_ecdsa(curve)) || (sm2 && curve != ECGPU_SM2) || (schnorr && curve != ECGPU_K256)) return curve_error(ctx, __func__);
+    if (h.bad(n && (!d || !k || !flag || !r_xy || !r_inf || !out_sig || !ok || (!schnorr && !z) || (ecdsa && !out_recid) ||
+                    (schnorr && msg_len && !msgs))))
+        return h.rc;
+    if (n == 0) return ECGPU_OK;
+    const size_t L = h.L;
+    return staged(ctx, n, {{d, &ctx->in0, schnorr ? 2 * L : L, SECRET}, {k, &ctx->in3, L, SECRET}, {flag, &ctx->sg_flag, 1},
+                           {schnorr ? nullptr : z, &ctx->in2, L}, {r_xy, &ctx->ec_xy, 2 * L}, {r_inf, &ctx->ec_inf, 1},
+                           {schnorr && msg_len ? msgs : nullptr, &ctx->in1, msg_len}},
+                  {{out_sig, &ctx->out0, 2 * L}, {ecdsa ? out_recid : nullptr, &ctx->out2, 1}, {ok, &ctx->out1, 1}},
+                  [&](auto in, auto o, size_t m) -> int {
+                      auto u8 = [&](int i) { return (const uint8_t*)in[i]; };
+                      if (ecdsa) {
+                          const int rc = dispatch(curve, [&](auto c) {
+                              launch_ecdsa_sign_finish<decltype(c)>(ctx->stream, u8(0), u8(1), u8(2), u8(3), u8(4), u8(5), m, normalize_s,
+                                                                    (uint8_t*)o[0], (uint8_t*)o[1], (uint8_t*)o[2]);
+                              return (int)ECGPU_OK;
+                          });
+                          if (rc != ECGPU_OK) return rc;
+                      } else if (sm2) {
+                          launch_sm2dsa_sign_finish<Sm2Params>(ctx->stream, u8(0), u8(1), u8(2), u8(3), u8(4), u8(5), m, (uint8_t*)o[0],
+                                                               (uint8_t*)o[2]);
+                      } else {
+                          launch_schnorr_sign_finish<K256Params>(ctx->stream, u8(0), u8(1), u8(2), u8(4), u8(5), u8(6), msg_len, m,
+                                                                 (uint8_t*)o[0], (uint8_t*)o[2]);
+                      }
+                      HIP_TRY(ctx, hipGetLastError());
+                      return (int)ECGPU_OK;
+                  }, STAGE_WHOLE);
+}
+
 int ecgpu_valu_probe(ecgpu_ctx* ctx, int which, double* ops_per_sec) {
     if (!check_ctx(ctx) || !ops_per_sec) return ECGPU_ERR_ARG;
     int rc;

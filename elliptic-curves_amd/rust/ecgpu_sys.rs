@@ -968,6 +968,24 @@ unsafe extern "C" {
         n: usize,
         out: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_selftest_sign_finish(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        scheme: c_int,
+        d: *const u8,
+        k: *const u8,
+        flag: *const u8,
+        z: *const u8,
+        r_xy: *const u8,
+        r_inf: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        n: usize,
+        normalize_s: c_int,
+        out_sig: *mut u8,
+        out_recid: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_valu_probe(ctx: *mut EcgpuCtx, which: c_int, ops_per_sec: *mut f64) -> c_int;
     pub fn ecgpu_last_timing(ctx: *const EcgpuCtx, name: *const c_char, ms: *mut f64) -> c_int;
     pub fn ecgpu_set_timing(ctx: *mut EcgpuCtx, on: c_int) -> c_int;

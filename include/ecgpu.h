@@ -855,6 +855,20 @@ int ecgpu_selftest_point(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p_xy,
                          const uint8_t *q_inf, size_t n, uint8_t *out_xy, uint8_t *out_inf);
 int ecgpu_selftest_point_raw(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p, const uint8_t *q, size_t n, uint8_t *out);
 
+/* Test infrastructure: the finish kernels of the signing entry points on stages the CALLER supplies, so that a test can hand them
+ * what no input of the pipelines produces (x(R) in [n, p), R at infinity, a cleared nonce flag beside a valid k, a Schnorr nonce that
+ * cancels e d').  Nothing runs before the kernel: `flag` is the nonce's verdict byte, r_xy the affine R (x || y) and r_inf its
+ * identity byte, as the nonce, fixed-base and normalisation kernels would have left them; k is the nonce AFTER the nonce kernel.
+ *   scheme 0  k_ecdsa_sign_finish (any ECDSA set): d, k, z of L bytes; out_sig = r || s, out_recid, ok.
+ *   scheme 1  k_sm2dsa_sign_finish (curve = ECGPU_SM2): z = the prehash e; out_recid unused (may be NULL).
+ *   scheme 2  k_schnorr_sign_finish (curve = ECGPU_K256): d = d' || x(P), 64 bytes per element; z unused (may be NULL); msgs = n
+ *             messages of msg_len bytes; out_recid unused.
+ * normalize_s applies to scheme 0 only.  ECGPU_ERR_ARG: unknown scheme or a missing array; ECGPU_ERR_CURVE: a curve the scheme
+ * does not exist over.  Not a signing interface: it checks nothing that ties R to k. */
+int ecgpu_selftest_sign_finish(ecgpu_ctx *ctx, int curve, int scheme, const uint8_t *d, const uint8_t *k, const uint8_t *flag,
+                               const uint8_t *z, const uint8_t *r_xy, const uint8_t *r_inf, const uint8_t *msgs, size_t msg_len, size_t n,
+                               int normalize_s, uint8_t *out_sig, uint8_t *out_recid, uint8_t *ok);
+
 /* Integer-VALU roof probe: runs a dependency-free v_mad_u64_u32 stream on every CU and returns
  * the measured 32x32->64 multiply-add rate in operations per second (SURVEY.md §8d "peak to
  * divide by").  `which` selects the instruction: 0 v_mad_u64_u32, 1 v_mul_lo_u32, 2 v_mul_hi_u32,

@@ -3,7 +3,16 @@
 // kernels' record layout, so that they can be checked against tests/sign_model.py without a GPU.  The multiplications by the
 // generator between the steps are not here: the test takes them from tests/hostcheck (fixed_base_mul_ct on the CPU).
 // Nothing here is linked into libecgpu.so.
+//
+// With -DHOSTCHECK_SIGN_MAIN the same source is a stand-alone program (built with -fsanitize=address,undefined by
+// tests/test_sign_vectors.py): it reads one finish-step record per line, all values in hex —
+//     E <curve id> <normalize_s> <d> <k> <flag> <z> <x(R) || y(R)> <r_inf>         the ECDSA finish step
+//     S <d' || x(P)> <k> <flag> <x(R) || y(R)> <r_inf> <message, "-" when empty>   the BIP340 finish step
+// — runs the step on heap buffers of exactly the record's size and prints what it wrote.
+#include <cstdio>
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "../../elliptic-curves_amd/csrc/ecgpu_sign.h"
 
@@ -153,3 +162,56 @@ int hs_schnorr_sign_finish(const uint8_t* dp, const uint8_t* k_in, const uint8_t
 }
 
 }  // extern "C"
+
+#ifdef HOSTCHECK_SIGN_MAIN
+namespace {
+std::vector<uint8_t> unhex(const std::string& s) {
+    std::vector<uint8_t> out;
+    if (s == "-") return out;
+    for (size_t i = 0; i + 1 < s.size(); i += 2) out.push_back((uint8_t)std::stoi(s.substr(i, 2), nullptr, 16));
+    return out;
+}
+void put(const char* name, const std::vector<uint8_t>& v) {
+    std::printf(" %s=", name);
+    for (uint8_t b : v) std::printf("%02x", b);
+}
+// exactly `v`'s bytes on the heap (one byte for an empty string: never a null data pointer)
+std::vector<uint8_t> exact(const std::vector<uint8_t>& v) { return v.empty() ? std::vector<uint8_t>(1) : v; }
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc != 2) return 2;
+    std::FILE* f = std::fopen(argv[1], "r");
+    if (!f) return 2;
+    static char kind[4], a[300], b[300], c[300], d[300], m[4096];
+    int curve = 0, norm = 0, kf = 0, ri = 0;
+    while (std::fscanf(f, "%3s", kind) == 1) {
+        if (kind[0] == 'E') {
+            if (std::fscanf(f, "%d %d %299s %299s %d %299s %299s %d", &curve, &norm, a, b, &kf, c, d, &ri) != 8) return 3;
+            size_t L = 0;
+            dispatch(curve, [&](auto cv) -> int { L = WireBytes<decltype(cv)>::value; return 0; });
+            const std::vector<uint8_t> dd = unhex(a), kk = unhex(b), zz = unhex(c), rxy = unhex(d);
+            if (!L || dd.size() != L || kk.size() != L || zz.size() != L || rxy.size() != 2 * L) return 3;
+            const std::vector<uint8_t> kflag(1, (uint8_t)kf), rinf(1, (uint8_t)ri);
+            std::vector<uint8_t> sig(2 * L), recid(1), ok(1);
+            if (hs_ecdsa_sign_finish(curve, dd.data(), kk.data(), kflag.data(), zz.data(), rxy.data(), rinf.data(), 1, norm, sig.data(),
+                                     recid.data(), ok.data()) != 0)
+                return 4;
+            put("sig", sig); put("recid", recid); put("ok", ok);
+        } else if (kind[0] == 'S') {
+            if (std::fscanf(f, "%299s %299s %d %299s %d %4095s", a, b, &kf, c, &ri, m) != 6) return 3;
+            const std::vector<uint8_t> dp = unhex(a), kk = unhex(b), rxy = unhex(c), msg = unhex(m), mb = exact(msg);
+            if (dp.size() != 64 || kk.size() != 32 || rxy.size() != 64) return 3;
+            const std::vector<uint8_t> kflag(1, (uint8_t)kf), rinf(1, (uint8_t)ri);
+            std::vector<uint8_t> sig(64), ok(1);
+            hs_schnorr_sign_finish(dp.data(), kk.data(), kflag.data(), rxy.data(), rinf.data(), mb.data(), msg.size(), 1, sig.data(), ok.data());
+            put("sig", sig); put("ok", ok);
+        } else {
+            return 3;
+        }
+        std::printf("\n");
+    }
+    std::fclose(f);
+    return 0;
+}
+#endif
