@@ -70,7 +70,9 @@ ABI_SYMBOLS = [
     "ecgpu_hash_to_curve_batch", "ecgpu_encode_to_curve_batch", "ecgpu_hash_to_scalar_batch", "ecgpu_map_to_curve_batch",
     "ecgpu_sm2_pke_encrypt_batch", "ecgpu_sm2_pke_decrypt_batch",
     "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch", "ecgpu_selftest_sign_finish",
+    "ecgpu_bign_sign_batch", "ecgpu_bign_sign_prehash_batch", "ecgpu_bign_sign_msg_batch", "ecgpu_selftest_bign_genk",
 ]
+SIGN_SCHEME_BIGN = 4
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
 
@@ -615,6 +617,59 @@ class Engine:
                                                         ctypes.c_size_t(msg_len), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
         return sig, ok
 
+    # ---- bign signing (bign256): keys and nonces are secrets; every record is little-endian ----
+    def _bign_sign_out(self, n, out, ok):
+        """out / ok: optional preallocated uint8 arrays (n*48, n) to write into, as for the SM2DSA signing methods"""
+        out = np.zeros(n * 48, np.uint8) if out is None else out
+        ok = np.zeros(n, np.uint8) if ok is None else ok
+        for a, need in ((out, n * 48), (ok, n)):
+            if a.dtype != np.uint8 or not a.flags.c_contiguous or a.size < need:
+                raise EcgpuError(ERR_ARG, "output buffer must be contiguous uint8 of at least %d bytes" % need)
+        return out, ok
+
+    def bign_sign(self, d, k, h, out=None, ok=None):
+        """bign with the caller's nonce (STB 34.101.45 section 7.1 steps 3-7; this form is ours, the reference has none): d, k, h
+        n*32 little-endian bytes each, h the prehash (any 32 bytes); returns (sig uint8[n*48] = S0 || S1, ok uint8[n])."""
+        dd, kk, hh = _host(d), _host(k), _host(h)
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("k", kk, n * 32); _need("h", hh, n * 32)
+        sig, ok = self._bign_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_bign_sign_batch(self._ctx, _hp(dd), _hp(kk), _hp(hh), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
+
+    def bign_sign_prehash(self, d, h, out=None, ok=None):
+        """`PrehashSigner::sign_prehash` (bign256): the nonce of the belt-based generator (STB 34.101.45 section 6.3.3, no additional
+        data), generated on the device; d, h n*32 bytes; returns (sig, ok)."""
+        dd, hh = _host(d), _host(h)
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("h", hh, n * 32)
+        sig, ok = self._bign_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_bign_sign_prehash_batch(self._ctx, _hp(dd), _hp(hh), ctypes.c_size_t(n), _hp(sig), _hp(ok)))
+        return sig, ok
+
+    def bign_sign_msg(self, d, msgs, msg_len, out=None, ok=None):
+        """`Signer::try_sign` (bign256): keys n*32, messages n*msg_len (one length per call, 0 allowed); H = belt-hash(message) and
+        the nonce are computed on the device; returns (sig, ok)."""
+        dd = _host(d)
+        mm = _host(msgs) if msg_len else None
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("msgs", mm, n * msg_len)
+        sig, ok = self._bign_sign_out(n, out, ok)
+        self._chk(self._lib.ecgpu_bign_sign_msg_batch(self._ctx, _hp(dd), _hp(mm), ctypes.c_size_t(msg_len), ctypes.c_size_t(n), _hp(sig),
+                                                      _hp(ok)))
+        return sig, ok
+
+    def selftest_bign_genk(self, d, h, bound):
+        """The generator kernels of bign signing with `bound` (32 little-endian bytes) in place of q (test infrastructure): returns
+        (k uint8[n*32], rounds uint32[n])."""
+        dd, hh, bb = _host(d), _host(h), _host(bound)
+        n = dd.size // 32
+        _need("d", dd, n * 32); _need("h", hh, n * 32); _need("bound", bb, 32)
+        k, rounds = np.zeros(n * 32, np.uint8), np.zeros(n, np.uint32)
+        self._chk(self._lib.ecgpu_selftest_bign_genk(self._ctx, _hp(dd), _hp(hh), _hp(bb), ctypes.c_size_t(n), _hp(k),
+                                                     _hp(rounds.view(np.uint8))))
+        return k, rounds
+
     def bign_verify(self, h, sigs, q_xy):
         """Batch bign verification on the prehash (bign256): h = belt-hash(message) as 32 bytes, signatures n*48 (S0 || S1), keys
         n*64; all little-endian."""
@@ -882,7 +937,8 @@ class Engine:
     def selftest_sign_finish(self, curve, scheme, d, k, flag, z, r_xy, r_inf, msgs=None, msg_len=0, normalize_s=False):
         """The finish kernels of the signing pipelines on stages the caller supplies (test infrastructure).  scheme 0: ECDSA
         (k_ecdsa_sign_finish) -> (sig, recid, ok); 1: SM2DSA, z = e -> (sig, ok); 2: BIP340, d = d' || x(P) records of 64 bytes,
-        z unused -> (sig, ok).  flag, r_xy, r_inf: what the nonce, fixed-base and normalisation kernels would have written."""
+        z unused -> (sig, ok); 4 (SIGN_SCHEME_BIGN): z = the raw prehash, the first 16 bytes of each r_xy record = S0 -> (sig of 48
+        bytes per element, ok).  flag, r_xy, r_inf: what the nonce, fixed-base and normalisation kernels would have written."""
         L = _field_bytes(curve)
         K, F, R, RI = _host(k), _host(flag), _host(r_xy), _host(r_inf)
         D, Z, M = _host(d), _host(z), _host(msgs)
@@ -893,6 +949,8 @@ class Engine:
         self._chk(self._lib.ecgpu_selftest_sign_finish(self._ctx, curve, int(scheme), _hp(D), _hp(K), _hp(F), _hp(Z), _hp(R), _hp(RI), _hp(M),
                                                        ctypes.c_size_t(msg_len), ctypes.c_size_t(n), int(bool(normalize_s)), _hp(sig),
                                                        _hp(recid), _hp(ok)))
+        if scheme == SIGN_SCHEME_BIGN:
+            sig = sig[:n * 48]
         return (sig, recid, ok) if scheme == 0 else (sig, ok)
 
     # ---- device-resident operations (torch uint8 CUDA tensors or raw device pointers) ----

@@ -801,6 +801,47 @@ int sm2dsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void
     return call.done();
 }
 
+// bign signing (ecgpu_bignsign.h), in the frame of sm2dsa_sign_dev.  d_k: the caller's nonce (the standard's steps 3-7); d_k == nullptr:
+// the belt-based generator (k_bign_genk, then k_bign_genk_retry once, by the rule of launch_rfc6979; its parked state lives in
+// sg_state).  from_msg: d_h holds n messages of msg_len bytes and H = belt-hash(message) goes to ec_e first (k_bign_hash_msg: messages
+// are public).  S0 is staged in sg_dp.  sg_k, sg_flag, sg_state, sg_dp, projective and affine R are wiped behind the last kernel.
+// There is no public `_dev` form of these calls yet: the host-pointer entry points have checked every argument before a chunk
+// reaches this function.
+int bign_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_h, size_t n, void* d_sig, void* d_ok,
+                  bool from_msg = false, size_t msg_len = 0) {
+    using C = Bign256Params;
+    constexpr int NS = Field<C>::NS;
+    int rc;
+    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
+    if (n == 0) return ECGPU_OK;
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
+                  {ctx->sg_dp, n * 16 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16},
+                  {ctx->sg_state, n * bign_genk_state_bytes<C>() + 16, !d_k}, {ctx->ec_e, n * 32 + 16, from_msg}});
+    if (call.rc != ECGPU_OK) return call.rc;
+    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *s0 = (uint8_t*)ctx->sg_dp.p;
+    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
+    call.mark(0);
+    if (from_msg) {
+        launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_h, msg_len, n, (uint8_t*)ctx->ec_e.p);
+        d_h = ctx->ec_e.p;
+    }
+    if (d_k)
+        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, k, flag);
+    else
+        launch_bign_genk<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_h, C::ORDER, n, ctx->rfc6979_cap, k, flag,
+                            (uint32_t*)ctx->sg_state.p);
+    launch_fixed_base_ct<C>(ctx->stream, k, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p,
+                            ctx->d_status);
+    call.mark(1);
+    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
+    launch_bign_sign_s0<C>(ctx->stream, (const uint8_t*)d_h, xy, n, s0);
+    launch_bign_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, k, flag, (const uint8_t*)d_h, s0, 16, inf, n, (uint8_t*)d_sig,
+                               (uint8_t*)d_ok);
+    call.mark(2);
+    return call.done();
+}
+
 // ---- SM2 public-key encryption (ecgpu_pke.h): the frame and the steps of ecdsa_sign_dev ----------------------------------------
 // seal (encrypt): d_scalar = k, d_point = P_B, d_in = M; C1 = k G is normalised straight into the caller's array (a public point),
 // (x2, y2) = k P_B into ec_xy, k_pke_seal writes C2 = d_out, C3 = d_c3 and ok (and zeroes the C1 of an element without a verdict).
@@ -2739,6 +2780,34 @@ int ecgpu_sm2dsa_sign_msg_batch(ecgpu_ctx* ctx, const uint8_t* distid, size_t di
                   });
 }
 
+// ---- bign signing: keys and nonces are staged as secrets; prehashes, messages and signatures are public ----
+// (host-pointer forms only, like the SM2DSA calls: bign_sign_dev is internal, every chunk reaches it through `staged`)
+int ecgpu_bign_sign_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* k, const uint8_t* h, size_t n, uint8_t* out_sig, uint8_t* ok) {
+    HostCall c(ctx, __func__, ECGPU_BIGN256);
+    if (c.bad(n && (!d || !k || !h || !out_sig || !ok))) return c.rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {k, &ctx->in3, 32, SECRET}, {h, &ctx->in2, 32}},
+                  {{out_sig, &ctx->out0, 48}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return bign_sign_dev(ctx, in[0], in[1], in[2], m, out[0], out[1]);
+                  });
+}
+
+int ecgpu_bign_sign_prehash_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* h, size_t n, uint8_t* out_sig, uint8_t* ok) {
+    HostCall c(ctx, __func__, ECGPU_BIGN256);
+    if (c.bad(n && (!d || !h || !out_sig || !ok))) return c.rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {h, &ctx->in2, 32}}, {{out_sig, &ctx->out0, 48}, {ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return bign_sign_dev(ctx, in[0], nullptr, in[1], m, out[0], out[1]); });
+}
+
+int ecgpu_bign_sign_msg_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* msgs, size_t msg_len, size_t n, uint8_t* out_sig,
+                              uint8_t* ok) {
+    HostCall c(ctx, __func__, ECGPU_BIGN256);
+    if (c.bad(n && (!d || !out_sig || !ok || (msg_len && !msgs)))) return c.rc;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {msg_len ? msgs : nullptr, &ctx->in1, msg_len}},
+                  {{out_sig, &ctx->out0, 48}, {ok, &ctx->out1, 1}}, [&](auto in, auto out, size_t m) {
+                      return bign_sign_dev(ctx, in[0], nullptr, in[1], m, out[0], out[1], true, msg_len);
+                  });
+}
+
 // ---- SM2 public-key encryption: k, d and the messages are staged as secrets; C1, C2 and C3 are public ----
 // (host-pointer forms only: sm2_pke_dev is internal, every chunk reaches it through `staged`)
 int ecgpu_sm2_pke_encrypt_batch(ecgpu_ctx* ctx, const uint8_t* pk_xy, const uint8_t* k, const uint8_t* msgs, size_t msg_len, size_t n,
@@ -2918,9 +2987,10 @@ int ecgpu_selftest_sign_finish(ecgpu_ctx* ctx, int curve, int scheme, const uint
                                int normalize_s, uint8_t* out_sig, uint8_t* out_recid, uint8_t* ok) {
     HostCall h(ctx, __func__, curve);
     if (h.rc != ECGPU_OK) return h.rc;
-    const bool ecdsa = scheme == 0, sm2 = scheme == 1, schnorr = scheme == 2;
-    if (!(ecdsa || sm2 || schnorr)) return arg_error(ctx, __func__);
-    if ((ecdsa && not_ecdsa(curve)) || (sm2 && curve != ECGPU_SM2) || (schnorr && curve != ECGPU_K256)) return curve_error(ctx, __func__);
+    const bool ecdsa = scheme == 0, sm2 = scheme == 1, schnorr = scheme == 2, bign = scheme == ECGPU_SIGN_SCHEME_BIGN;
+    if (!(ecdsa || sm2 || schnorr || bign)) return arg_error(ctx, __func__);
+    if ((ecdsa && not_ecdsa(curve)) || (sm2 && curve != ECGPU_SM2) || (schnorr && curve != ECGPU_K256) || (bign && curve != ECGPU_BIGN256))
+        return curve_error(ctx, __func__);
     if (h.bad(n && (!d || !k || !flag || !r_xy || !r_inf || !out_sig || !ok || (!schnorr && !z) || (ecdsa && !out_recid) ||
                     (schnorr && msg_len && !msgs))))
         return h.rc;
@@ -2929,7 +2999,7 @@ int ecgpu_selftest_sign_finish(ecgpu_ctx* ctx, int curve, int scheme, const uint
     return staged(ctx, n, {{d, &ctx->in0, schnorr ? 2 * L : L, SECRET}, {k, &ctx->in3, L, SECRET}, {flag, &ctx->sg_flag, 1},
                            {schnorr ? nullptr : z, &ctx->in2, L}, {r_xy, &ctx->ec_xy, 2 * L}, {r_inf, &ctx->ec_inf, 1},
                            {schnorr && msg_len ? msgs : nullptr, &ctx->in1, msg_len}},
-                  {{out_sig, &ctx->out0, 2 * L}, {ecdsa ? out_recid : nullptr, &ctx->out2, 1}, {ok, &ctx->out1, 1}},
+                  {{out_sig, &ctx->out0, bign ? 48 : 2 * L}, {ecdsa ? out_recid : nullptr, &ctx->out2, 1}, {ok, &ctx->out1, 1}},
                   [&](auto in, auto o, size_t m) -> int {
                       auto u8 = [&](int i) { return (const uint8_t*)in[i]; };
                       if (ecdsa) {
@@ -2942,12 +3012,39 @@ int ecgpu_selftest_sign_finish(ecgpu_ctx* ctx, int curve, int scheme, const uint
                       } else if (sm2) {
                           launch_sm2dsa_sign_finish<Sm2Params>(ctx->stream, u8(0), u8(1), u8(2), u8(3), u8(4), u8(5), m, (uint8_t*)o[0],
                                                                (uint8_t*)o[2]);
+                      } else if (bign) {                       // z = the raw prehash, S0 = the first 16 bytes of each r_xy record
+                          launch_bign_sign_finish<Bign256Params>(ctx->stream, u8(0), u8(1), u8(2), u8(3), u8(4), 64, u8(5), m,
+                                                                 (uint8_t*)o[0], (uint8_t*)o[2]);
                       } else {
                           launch_schnorr_sign_finish<K256Params>(ctx->stream, u8(0), u8(1), u8(2), u8(4), u8(5), u8(6), msg_len, m,
                                                                  (uint8_t*)o[0], (uint8_t*)o[2]);
                       }
                       HIP_TRY(ctx, hipGetLastError());
                       return (int)ECGPU_OK;
+                  }, STAGE_WHOLE);
+}
+
+// The generator kernels of bign signing with the caller's bound in place of q (test infrastructure: tests/test_gpu_bignsign.py).
+// The prehash is reduced mod q as in the signing calls; k_bign_genk and k_bign_genk_retry run as bign_sign_dev launches them.
+// out_k: the accepted candidate (1 where the cap was reached), out_rounds: the generator's round counter afterwards (4 bytes per element).
+int ecgpu_selftest_bign_genk(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* h, const uint8_t* bound, size_t n, uint8_t* out_k,
+                             uint8_t* out_rounds) {
+    using C = Bign256Params;
+    HostCall c(ctx, __func__, ECGPU_BIGN256);
+    if (c.bad(!bound || (n && (!d || !h || !out_k || !out_rounds)))) return c.rc;
+    if (n == 0) return ECGPU_OK;
+    uint32_t bw[8];
+    for (int j = 0; j < 8; j++)
+        bw[j] = (uint32_t)bound[4 * j] | (uint32_t)bound[4 * j + 1] << 8 | (uint32_t)bound[4 * j + 2] << 16 | (uint32_t)bound[4 * j + 3] << 24;
+    return staged(ctx, n, {{d, &ctx->in0, 32, SECRET}, {h, &ctx->in2, 32}},
+                  {{out_k, &ctx->out0, 32, SECRET}, {out_rounds, &ctx->out1, 4}}, [&](auto in, auto o, size_t m) -> int {
+                      DevCall call(ctx, WIPE_SIGN, {{ctx->sg_flag, m + 16}, {ctx->sg_state, m * bign_genk_state_bytes<C>() + 16}});
+                      if (call.rc != ECGPU_OK) return call.rc;
+                      uint32_t* state = (uint32_t*)ctx->sg_state.p;
+                      launch_bign_genk<C>(ctx->stream, (const uint8_t*)in[0], (const uint8_t*)in[1], bw, m, ctx->rfc6979_cap, (uint8_t*)o[0],
+                                          (uint8_t*)ctx->sg_flag.p, state);
+                      HIP_TRY(ctx, hipMemcpyAsync(o[1], state + 16 * m, m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                      return call.done_unmarked();
                   }, STAGE_WHOLE);
 }
 

@@ -40,16 +40,55 @@ struct Belt {
     // G_r: the S-box on the four bytes of a word, then a left rotation by r.  `sb` = the table the caller wants the 2,700 lookups
     // of one signature to go to: Belt::H itself on the host, a copy in LDS in the kernels (normalise + k_bign_finish per
     // 2^20 signatures: 1.60 -> 0.44 ms, profiles/r03/bign_verify_rate.txt).
-    template <int R>
-    static ECGPU_HD uint32_t g(const uint8_t* sb, uint32_t u) {
-        const uint32_t v = (uint32_t)sb[u & 255u] | (uint32_t)sb[(u >> 8) & 255u] << 8 | (uint32_t)sb[(u >> 16) & 255u] << 16 |
-                           (uint32_t)sb[u >> 24] << 24;
+    static ECGPU_HD uint32_t sub(const uint8_t* sb, uint32_t u) {
+        return (uint32_t)sb[u & 255u] | (uint32_t)sb[(u >> 8) & 255u] << 8 | (uint32_t)sb[(u >> 16) & 255u] << 16 |
+               (uint32_t)sb[u >> 24] << 24;
+    }
+
+    // The second access policy, for SECRET words (the nonce generator of bign signing, ecgpu_bignsign.h): the same four lookups
+    // with no memory access and no branch.  The table is 32 pools of 8 bytes, each a pair of 32-bit constants.  Per pool one byte
+    // permute with the selector u & 0x07070707 yields the candidates of all four lookups at once (v_perm_b32 on the device, shifts
+    // on the host); a 5-level tree of 31 bitwise selects (v_bfi_b32) under byte-wide masks spread from bits 3..7 of each byte of u
+    // picks the pool.  Pass `Belt::CtSbox()` where the table form takes the table.
+    struct CtSbox {};
+    static ECGPU_HD constexpr uint32_t pool_word(int j) {
+        return (uint32_t)H[4 * j] | (uint32_t)H[4 * j + 1] << 8 | (uint32_t)H[4 * j + 2] << 16 | (uint32_t)H[4 * j + 3] << 24;
+    }
+    // byte j of the result = byte (sel_j & 7) of the 8 bytes lo (bytes 0..3) || hi (bytes 4..7)
+    static ECGPU_HD uint32_t pick8(uint32_t hi, uint32_t lo, uint32_t sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        return __builtin_amdgcn_perm(hi, lo, sel);
+#else
+        const uint64_t v = (uint64_t)hi << 32 | lo;
+        uint32_t r = 0;
+        for (int j = 0; j < 4; j++) r |= (uint32_t)((v >> (8 * ((sel >> (8 * j)) & 7u))) & 0xffu) << (8 * j);
+        return r;
+#endif
+    }
+    static ECGPU_HD uint32_t sub(CtSbox, uint32_t u) {
+        const uint32_t sel = u & 0x07070707u;
+        uint32_t t[32];
+#pragma unroll
+        for (int p = 0; p < 32; p++) t[p] = pick8(pool_word(2 * p + 1), pool_word(2 * p), sel);
+#pragma unroll
+        for (int lvl = 0; lvl < 5; lvl++) {
+            const uint32_t m = ((u >> (3 + lvl)) & 0x01010101u) * 0xffu;       // 0xff in every byte whose bit 3 + lvl is set
+#pragma unroll
+            for (int p = 0; p < (16 >> lvl); p++) t[p] = (t[2 * p + 1] & m) | (t[2 * p] & ~m);
+        }
+        return t[0];
+    }
+
+    template <int R, class SB>
+    static ECGPU_HD uint32_t g(SB sb, uint32_t u) {
+        const uint32_t v = sub(sb, u);
         return (v << R) | (v >> (32 - R));
     }
 
     // y <- belt-block(x) under the 256-bit key: eight rounds over the words a, b, c, d (all words little-endian), key words
     // K[7i - 6 .. 7i] = key[(7i - 7 .. 7i - 1) mod 8]
-    static ECGPU_HD void block(const uint8_t* sb, uint32_t* y, const uint32_t* x, const uint32_t* key) {
+    template <class SB>
+    static ECGPU_HD void block(SB sb, uint32_t* y, const uint32_t* x, const uint32_t* key) {
         uint32_t a = x[0], b = x[1], c = x[2], d = x[3];
 #pragma unroll
         for (int i = 1; i <= 8; i++) {
@@ -74,7 +113,8 @@ struct Belt {
     //     s <- s xor sigma1(u),   h <- sigma2(u)
     // sigma1(u) = belt-block(u3 xor u4, u1 || u2) xor u3 xor u4;
     // sigma2(u) = (belt-block(u1, sigma1(u) || u4) xor u1) || (belt-block(u2, (sigma1(u) xor 1^128) || u3) xor u2)
-    static ECGPU_HD void step(const uint8_t* sb, uint32_t* s, uint32_t* h, const uint32_t* x) {
+    template <class SB>
+    static ECGPU_HD void step(SB sb, uint32_t* s, uint32_t* h, const uint32_t* x) {
         uint32_t t[4], s1[4], key[8], y1[4], y2[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) t[j] = h[j] ^ h[4 + j];
@@ -103,8 +143,8 @@ struct Belt {
     // out (8 little-endian words = the 32 digest bytes in order) = belt-hash(pieces[0] || ... || pieces[NP - 1]).
     // Blocks of 32 bytes, the last one filled with zeros; then one more step on <bit length>_128 || s.  ONE call site of `step`
     // (the last pass of the loop is the finalisation), so the three unrolled block encryptions are inlined once.
-    template <int NP>
-    static ECGPU_HD void hash_pieces(const uint8_t* sb, uint32_t* out, const HashPiece* pc) {
+    template <int NP, class SB>
+    static ECGPU_HD void hash_pieces(SB sb, uint32_t* out, const HashPiece* pc) {
         size_t total = 0;
 #pragma unroll
         for (int t = 0; t < NP; t++) total += pc[t].n;
@@ -146,6 +186,28 @@ struct Belt {
                     }
                     x[j] = word;
                 }
+            }
+            step(sb, s, h, x);
+        }
+#pragma unroll
+        for (int j = 0; j < 8; j++) out[j] = h[j];
+    }
+
+    // out = belt-hash of a message of 33 .. 64 bytes handed over as its sixteen little-endian words m (zeros behind the message):
+    // two blocks and the finalisation.  For SECRET messages (theta of the bign nonce generator): no byte is fetched by a walking
+    // pointer as in hash_pieces, the block of each pass is selected by the pass counter.  ONE call site of `step`.
+    template <class SB>
+    static ECGPU_HD void hash_two_blocks(SB sb, uint32_t* out, const uint32_t* m, uint32_t total_bytes) {
+        uint32_t s[4] = {0, 0, 0, 0}, h[8];
+#pragma unroll
+        for (int j = 0; j < 8; j++) h[j] = pool_word(j);
+#pragma unroll 1
+        for (int blk = 0; blk < 3; blk++) {
+            uint32_t x[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t fin = j == 0 ? total_bytes * 8u : j < 4 ? 0u : s[j - 4];
+                x[j] = blk == 0 ? m[j] : blk == 1 ? m[8 + j] : fin;
             }
             step(sb, s, h, x);
         }

@@ -3,6 +3,7 @@
 #include "ecgpu_sign.h"
 #include "ecgpu_pke.h"
 #include "ecgpu_sm2sign.h"
+#include "ecgpu_bignsign.h"
 #include "ecgpu_launch.h"
 
 namespace ecgpu {
@@ -67,6 +68,29 @@ void sm2dsa_sign_finish_impl(hipStream_t s, const uint8_t* d, const uint8_t* k, 
     if constexpr (Sm2Sign<C>::value)
         hipLaunchKernelGGL(k_sm2dsa_sign_finish<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, k, k_flag, e, r_xy, r_inf, n, sig, ok);
 }
+
+// bign signing exists over bign-curve256v1 with belt only (ecgpu_bignsign.h): the other curves' translation units hold none of its
+// kernels
+template <class C>
+void bign_genk_impl(hipStream_t s, const uint8_t* d, const uint8_t* h, const uint32_t* bound, size_t n, int cap, uint8_t* k_out,
+                    uint8_t* flag, uint32_t* state) {
+    if constexpr (BignSign<C>::value) {
+        BignBound b;
+        for (int j = 0; j < 8; j++) b.w[j] = bound[j];
+        hipLaunchKernelGGL(k_bign_genk<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, h, b, n, k_out, flag, state);
+        hipLaunchKernelGGL(k_bign_genk_retry<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, b, n, cap, k_out, flag, state);
+    }
+}
+template <class C>
+void bign_sign_s0_impl(hipStream_t s, const uint8_t* h, const uint8_t* r_xy, size_t n, uint8_t* s0_out) {
+    if constexpr (BignSign<C>::value) hipLaunchKernelGGL(k_bign_sign_s0<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, h, r_xy, n, s0_out);
+}
+template <class C>
+void bign_sign_finish_impl(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* h, const uint8_t* s0,
+                           size_t s0_stride, const uint8_t* r_inf, size_t n, uint8_t* sig, uint8_t* ok) {
+    if constexpr (BignSign<C>::value)
+        hipLaunchKernelGGL(k_bign_sign_finish<C>, dim3(sign_grid(n)), dim3(BLOCK), 0, s, d, k, k_flag, h, s0, s0_stride, r_inf, n, sig, ok);
+}
 }  // namespace
 
 template <> void launch_sign_nonce_load<CurveT>(hipStream_t s, const uint8_t* k_in, size_t n, uint8_t* k_out, uint8_t* flag) {
@@ -121,6 +145,19 @@ template <> void launch_sm2dsa_sign_finish<CurveT>(hipStream_t s, const uint8_t*
                                                    const uint8_t* e, const uint8_t* r_xy, const uint8_t* r_inf, size_t n, uint8_t* sig,
                                                    uint8_t* ok) {
     sm2dsa_sign_finish_impl<CurveT>(s, d, k, k_flag, e, r_xy, r_inf, n, sig, ok);
+}
+template <> size_t bign_genk_state_bytes<CurveT>() { return BignSign<CurveT>::value ? BIGN_GENK_STATE_WORDS * sizeof(uint32_t) : 0; }
+template <> void launch_bign_genk<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* h, const uint32_t* bound, size_t n, int cap,
+                                          uint8_t* k_out, uint8_t* flag, uint32_t* state) {
+    bign_genk_impl<CurveT>(s, d, h, bound, n, cap, k_out, flag, state);
+}
+template <> void launch_bign_sign_s0<CurveT>(hipStream_t s, const uint8_t* h, const uint8_t* r_xy, size_t n, uint8_t* s0_out) {
+    bign_sign_s0_impl<CurveT>(s, h, r_xy, n, s0_out);
+}
+template <> void launch_bign_sign_finish<CurveT>(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag,
+                                                 const uint8_t* h, const uint8_t* s0, size_t s0_stride, const uint8_t* r_inf, size_t n,
+                                                 uint8_t* sig, uint8_t* ok) {
+    bign_sign_finish_impl<CurveT>(s, d, k, k_flag, h, s0, s0_stride, r_inf, n, sig, ok);
 }
 
 }  // namespace ecgpu

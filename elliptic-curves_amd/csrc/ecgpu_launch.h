@@ -141,6 +141,17 @@ template <class C> void launch_sm2_sign_e(hipStream_t s, const uint8_t* distid, 
 template <class C> void launch_sm2_rfc6979(hipStream_t s, const uint8_t* d, const uint8_t* e, size_t n, uint8_t* k_out, uint8_t* flag);
 template <class C> void launch_sm2dsa_sign_finish(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* e,
                                                   const uint8_t* r_xy, const uint8_t* r_inf, size_t n, uint8_t* sig, uint8_t* ok);
+// bign signing (ecgpu_bignsign.h; launches nothing for a curve other than bign256).  genk: theta and rounds 1-4 of the belt-based
+// generator (k_bign_genk: the candidate, 1 in place of a rejected one, its verdict, the parked state of bign_genk_state_bytes<C>() bytes
+// per element), then k_bign_genk_retry once (the deliberately variable-time one); bound: eight little-endian words, q in the signing
+// calls; cap: candidates per element.  s0: 16 bytes per element from the affine R and the raw prehash; finish: S0 || S1 and ok
+template <class C> size_t bign_genk_state_bytes();
+template <class C> void launch_bign_genk(hipStream_t s, const uint8_t* d, const uint8_t* h, const uint32_t* bound, size_t n, int cap,
+                                         uint8_t* k_out, uint8_t* flag, uint32_t* state);
+template <class C> void launch_bign_sign_s0(hipStream_t s, const uint8_t* h, const uint8_t* r_xy, size_t n, uint8_t* s0_out);
+template <class C> void launch_bign_sign_finish(hipStream_t s, const uint8_t* d, const uint8_t* k, const uint8_t* k_flag, const uint8_t* h,
+                                                const uint8_t* s0, size_t s0_stride, const uint8_t* r_inf, size_t n, uint8_t* sig,
+                                                uint8_t* ok);
 
 // ---- group "h2c": RFC 9380 hash-to-curve (ecgpu_h2c.h); k256, p256 and p384 only (h2c_supported), nothing is launched for the others ----
 template <class C> bool h2c_supported();

@@ -625,6 +625,42 @@ pub mod gpu {
         Some(sig.chunks(64).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
     }
 
+    /// Batch form of `PrehashSigner::sign_prehash` of `bignp256::ecdsa::SigningKey` (bignp256/src/ecdsa/signing.rs:110-161,164-176):
+    /// `prehashes` are exactly 32 bytes each, any value (the nonce generator and S1 take them reduced mod q, the S0 hash absorbs
+    /// them as they are).  The belt-based nonce generator (`bign_genk::KGenerator<BeltBlock>`, no additional data), R = k G on the
+    /// uniform-schedule kernel, S0 and S1 are computed on the device (`ecgpu_bign_sign_prehash_batch`); the wire copy of the keys
+    /// (`to_repr`: little-endian) is wiped here, the device side by the library.  `None` per element where the reference returns
+    /// `Err` (S0 = 0 or S1 = 0 in `Signature::from_scalars`).  The signature is S0 || S1, 48 bytes.
+    pub fn bign_sign_prehash_batch(keys: &[NonZeroScalar<bignp256::BignP256>], prehashes: &[[u8; 32]]) -> Option<Vec<Option<[u8; 48]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = keys.len();
+        assert!(prehashes.len() == n);
+        let mut d = Zeroizing::new(Vec::with_capacity(32 * n));
+        for k in keys {
+            d.extend_from_slice(&k.to_repr());
+        }
+        let (mut sig, mut ok) = (vec![0u8; 48 * n], vec![0u8; n]);
+        check(unsafe {
+            ecgpu_bign_sign_prehash_batch(eng.0, d.as_ptr(), prehashes.as_ptr() as *const u8, n, sig.as_mut_ptr(), ok.as_mut_ptr())
+        })?;
+        Some(sig.chunks(48).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
+    }
+
+    /// Batch form of `Signer::try_sign` of `bignp256::ecdsa::SigningKey` (bignp256/src/ecdsa/signing.rs:110-161,164-176) for messages
+    /// of one length: H = belt-hash(message) and the prehash form above all run on the device (`ecgpu_bign_sign_msg_batch`).
+    pub fn bign_sign_batch(keys: &[NonZeroScalar<bignp256::BignP256>], msgs: &[u8], msg_len: usize) -> Option<Vec<Option<[u8; 48]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = keys.len();
+        assert!(msgs.len() == n * msg_len);
+        let mut d = Zeroizing::new(Vec::with_capacity(32 * n));
+        for k in keys {
+            d.extend_from_slice(&k.to_repr());
+        }
+        let (mut sig, mut ok) = (vec![0u8; 48 * n], vec![0u8; n]);
+        check(unsafe { ecgpu_bign_sign_msg_batch(eng.0, d.as_ptr(), msgs.as_ptr(), msg_len, n, sig.as_mut_ptr(), ok.as_mut_ptr()) })?;
+        Some(sig.chunks(48).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
+    }
+
     /// Batch form of `hash2curve::GroupDigest::hash_from_bytes(&[msg], &[dst])` (hash2curve/src/group_digest.rs) for the curves
     /// with a suite on the device (k256, p256, p384): `msgs` holds `n` messages of `msg_len` bytes each, `dst` is the one domain
     /// separation tag of the batch (not empty: `Domain::xmd` refuses that, and so does the library).

@@ -40,6 +40,7 @@ pub const ECGPU_TABLE_ADAPTIVE: c_int = 0;
 pub const ECGPU_TABLE_EAGER: c_int = 1;
 pub const ECGPU_EXCHANGE_PEER: c_int = 1;
 pub const ECGPU_EXCHANGE_RCCL: c_int = 2;
+pub const ECGPU_SIGN_SCHEME_BIGN: c_int = 4;
 
 #[link(name = "ecgpu")]
 unsafe extern "C" {
@@ -697,6 +698,32 @@ unsafe extern "C" {
         out_sig: *mut u8,
         ok: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_bign_sign_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        k: *const u8,
+        h: *const u8,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_bign_sign_prehash_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        h: *const u8,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_bign_sign_msg_batch(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        msgs: *const u8,
+        msg_len: usize,
+        n: usize,
+        out_sig: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_batch_mul_ct_xyz(
         ctx: *mut EcgpuCtx,
         curve: c_int,
@@ -985,6 +1012,15 @@ unsafe extern "C" {
         out_sig: *mut u8,
         out_recid: *mut u8,
         ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_selftest_bign_genk(
+        ctx: *mut EcgpuCtx,
+        d: *const u8,
+        h: *const u8,
+        bound: *const u8,
+        n: usize,
+        out_k: *mut u8,
+        out_rounds: *mut u8,
     ) -> c_int;
     pub fn ecgpu_valu_probe(ctx: *mut EcgpuCtx, which: c_int, ops_per_sec: *mut f64) -> c_int;
     pub fn ecgpu_last_timing(ctx: *const EcgpuCtx, name: *const c_char, ms: *mut f64) -> c_int;

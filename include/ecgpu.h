@@ -627,8 +627,7 @@ int ecgpu_schnorr_sign_raw_batch_dev(ecgpu_ctx *ctx, const void *d_sk, const voi
  *   b || xG || yG || xA || yA) and e = SM3(Z || M) on the device, then the RFC 6979 form.  distid: distid_len <= 8191 bytes, one
  *   identifier per call (ECGPU_ERR_ARG above that); msgs: n*msg_len bytes, one uniform length per call, 0 allowed — the argument
  *   rules of ecgpu_sm2dsa_verify_msg_batch.
- * Out of scope: `RandomizedPrehashSigner` (32 bytes of additional data make the generator's HMAC message three blocks) and bign
- * signing (its nonce is belt-based).
+ * Out of scope: `RandomizedPrehashSigner` (32 bytes of additional data make the generator's HMAC message three blocks).
  * Host-pointer forms only, like the SM2 encryption calls below: there is no public `_dev` name yet (every chunk of a call reaches
  * the internal device-pointer pipeline through the staging path, from 2^19 elements on piece by piece under the transfers).  On
  * an asynchronous context a call first waits for the queued work and runs synchronously, as every host-pointer call does. */
@@ -637,6 +636,45 @@ int ecgpu_sm2dsa_sign_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *k, 
 int ecgpu_sm2dsa_sign_rfc6979_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *e, size_t n, uint8_t *out_sig, uint8_t *ok);
 int ecgpu_sm2dsa_sign_msg_batch(ecgpu_ctx *ctx, const uint8_t *distid, size_t distid_len, const uint8_t *d, const uint8_t *msgs,
                                 size_t msg_len, size_t n, uint8_t *out_sig, uint8_t *ok);
+
+/* ---- batch bign signing (STB 34.101.45-2013 section 7.1, l = 128): the signing half of `bignp256::ecdsa` ---------------------
+ * bign-curve256v1 only, hence no `curve` argument (as for ecgpu_bign_verify_batch).  d, k, h: 32-byte LITTLE-endian records, as
+ * every bign256 record; out_sig: n*48 bytes S0 (16) || S1 (32), the layout ecgpu_bign_verify_batch takes; ok: one byte per element.
+ *     h = prehash mod q,  R = k G,  S0 = belt-hash(OID(h) || <x(R)>_256 || prehash)[..16],  S1 = k - h - (S0 + 2^128) d mod q
+ * The prehash enters twice and NOT as the same value (bignp256/src/ecdsa/signing.rs:117-123, 141-144): the nonce generator and S1
+ * use the prehash REDUCED mod q, the S0 hash absorbs the RAW 32 bytes.  The two differ exactly when the prehash is >= q as an
+ * integer; both calls take any 32 bytes.
+ * An element that cannot be signed never fails the batch: it gets a zero record and ok[i] = 0, and its neighbours are untouched.
+ * Refused: d outside [1, q); a caller's k outside [1, q); S0 = 0 or S1 = 0 (`Signature::from_bytes`, bignp256/src/ecdsa.rs:85-87).
+ * R = k G is the kernel of ecgpu_batch_mul_base_ct.  In the generator, load and finish kernels no branch and no address depends on
+ * d, k, the prehash or anything derived from them (tools/ct_isa_check.py --unit bignsign; tests/test_bignsign_isa.py): belt's
+ * S-box, which the generator looks up at secret indices, is computed there from byte permutes and bitwise selects over constants,
+ * without a table in memory.  S0 hashes public values only (R can be recomputed from the signature and the public key) and uses
+ * the table.  Everything derived from d or k on the device (the nonces and their verdicts, the generator's parked state, S0,
+ * projective and affine R, the staged copies of d and k) is zeroed behind the last kernel in stream order, and ecgpu_wipe covers
+ * the same buffers.
+ *
+ * ecgpu_bign_sign_batch - the standard's steps 3-7 with the caller's nonce.  THIS FORM IS OURS: the reference has no entry point
+ *   that takes a nonce; it exists for known answers and for callers with their own RNG.  h: the prehash, any 32 bytes.
+ * ecgpu_bign_sign_prehash_batch - `PrehashSigner::sign_prehash` (signing.rs:110-161): the nonce of STB 34.101.45 section 6.3.3
+ *   (`bign_genk::KGenerator<BeltBlock>`), with additional data t empty, as the reference passes `&[]`:
+ *       theta = belt-hash(OID(h) || <d>_256 || t),  r1 || r2 = <prehash mod q>_256,
+ *       i = 1, 2, ...:  s = r1;  r1 = belt-block(s, theta) xor r2 xor <i>_128;  r2 = s;
+ *       every fourth round r1 || r2 is a candidate, accepted if it is in (0, q).
+ *   The retry rule: the first candidate (round 4) comes from a kernel of uniform schedule; an element whose candidate was rejected
+ *   goes on in k_bign_genk_retry, which is launched once per call as k_rfc6979_retry is and is the one deliberately variable-time
+ *   piece: its trip count follows the REJECTED candidates, never used.  With q > 2^256 - 2^129 that is one element in 2^130.  After 128
+ *   rejected candidates the element gets ok = 0.
+ * ecgpu_bign_sign_msg_batch - `Signer::try_sign` (signing.rs:164-176): H = belt-hash(message) on the device, then the prehash
+ *   form.  msgs: n*msg_len bytes, one uniform length per call, 0 allowed.
+ * Out of scope: additional data t (`bign_genk` with a non-empty t), public `_dev` names, ecgpu_group_* forms, the C++ mirror.
+ * Host-pointer forms only, like the SM2DSA calls above: there is no public `_dev` name yet.  On an asynchronous context a call
+ * first waits for the queued work and runs synchronously, as every host-pointer call does. */
+int ecgpu_bign_sign_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *k, const uint8_t *h, size_t n, uint8_t *out_sig,
+                          uint8_t *ok);
+int ecgpu_bign_sign_prehash_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *h, size_t n, uint8_t *out_sig, uint8_t *ok);
+int ecgpu_bign_sign_msg_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *msgs, size_t msg_len, size_t n, uint8_t *out_sig,
+                              uint8_t *ok);
 
 /* The same two with projective points: point i is the record X || Y || Z of the wire format above (3L bytes, no flag array),
  * as the reference's `Mul<Scalar>` and `lincomb` take a `ProjectivePoint`.  For every input the results and the return code
@@ -863,11 +901,23 @@ int ecgpu_selftest_point_raw(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p
  *   scheme 1  k_sm2dsa_sign_finish (curve = ECGPU_SM2): z = the prehash e; out_recid unused (may be NULL).
  *   scheme 2  k_schnorr_sign_finish (curve = ECGPU_K256): d = d' || x(P), 64 bytes per element; z unused (may be NULL); msgs = n
  *             messages of msg_len bytes; out_recid unused.
+ *   scheme 4  k_bign_sign_finish (ECGPU_SIGN_SCHEME_BIGN; curve = ECGPU_BIGN256): z = the RAW prehash; the first 16 bytes of each
+ *             64-byte r_xy record are S0, handed to the kernel directly (0, 1, 2^128 - 1: the stages no input produces); out_sig =
+ *             S0 || S1, 48 bytes per element; out_recid unused.  (3 is not a scheme.)
  * normalize_s applies to scheme 0 only.  ECGPU_ERR_ARG: unknown scheme or a missing array; ECGPU_ERR_CURVE: a curve the scheme
  * does not exist over.  Not a signing interface: it checks nothing that ties R to k. */
+enum { ECGPU_SIGN_SCHEME_BIGN = 4 };
 int ecgpu_selftest_sign_finish(ecgpu_ctx *ctx, int curve, int scheme, const uint8_t *d, const uint8_t *k, const uint8_t *flag,
                                const uint8_t *z, const uint8_t *r_xy, const uint8_t *r_inf, const uint8_t *msgs, size_t msg_len, size_t n,
                                int normalize_s, uint8_t *out_sig, uint8_t *out_recid, uint8_t *ok);
+
+/* Test infrastructure: the nonce generator kernels of bign signing (k_bign_genk, k_bign_genk_retry) with the caller's 32-byte
+ * little-endian `bound` in place of q.  No input makes a candidate >= q with the real q; with bound = 2^254 three candidates in four
+ * are rejected, which runs the retry path on hardware.  d: the keys, h: the prehashes (reduced mod q first, as in the signing
+ * calls); out_k: n*32 bytes, the accepted candidate; out_rounds: n*4 bytes, the round count as a little-endian 32-bit integer (a
+ * multiple of 4).  An element that reached the cap of 128 candidates gets k = 1 and 512 rounds. */
+int ecgpu_selftest_bign_genk(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *h, const uint8_t *bound, size_t n, uint8_t *out_k,
+                             uint8_t *out_rounds);
 
 /* Integer-VALU roof probe: runs a dependency-free v_mad_u64_u32 stream on every CU and returns
  * the measured 32x32->64 multiply-add rate in operations per second (SURVEY.md §8d "peak to

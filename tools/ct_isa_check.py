@@ -19,6 +19,12 @@ untrusted ciphertext) is checked by k_pke_point, a kernel of its own that branch
     python tools/ct_isa_check.py --unit sm2sign --curve Sm2Params [--kernels ...]
 the SM2DSA signing kernels (csrc/ecgpu_sm2sign.h, translation unit ecgpu_inst_sign.hip; sm2 only): d, k, e, the affine PA and R,
 the HMAC-SM3 state and the candidate are all loaded records or derived from them; distid_len, msg_len and n are kernel arguments.
+    python tools/ct_isa_check.py --unit bignsign --curve Bign256Params [--must-flag k_bign_genk_retry,k_bign_sign_s0]
+the bign signing kernels (csrc/ecgpu_bignsign.h, translation unit ecgpu_inst_sign.hip; bign256 only): d, k, the prehash, theta, the
+generator's state and S0 are all loaded records or derived from them; the bound q, the S0 stride and n are kernel arguments.  The
+generator's S-box lookups are computed (Belt::CtSbox), so k_bign_genk holds no data-dependent address.  The two kernels that MUST be
+reported show that the analysis sees what it is there for in this unit: k_bign_genk_retry loops on the rejected candidates, and
+k_bign_sign_s0 (public inputs) indexes the S-box table in LDS by loaded bytes.
 
 How: the translation unit is compiled to assembly (hipcc -S --offload-device-only; no GPU needed) and every selected kernel
 goes through a forward taint analysis over its control-flow graph (register-precise, iterated to a fixed point):
@@ -384,6 +390,9 @@ UNITS = {
     "h2c": ("ecgpu_inst_h2c.hip", "k_h2c_expand,k_h2c_map"),
     "pke": ("ecgpu_inst_sign.hip", "k_pke_load,k_pke_seal,k_pke_open"),
     "sm2sign": ("ecgpu_inst_sign.hip", "k_sm2_sign_e,k_sm2_rfc6979,k_sm2dsa_sign_finish"),
+    # (names are matched inside the mangled ones: the `I` that opens the template arguments keeps k_bign_genk_retry, which is
+    # variable-time on purpose, out of the default list)
+    "bignsign": ("ecgpu_inst_sign.hip", "k_bign_genkI,k_bign_sign_finish,k_sign_nonce_load"),
 }
 
 
@@ -416,7 +425,7 @@ def check(asm, wanted, verbose=False, seen_names=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="append")
-    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, the SM2 encryption kernels, or the SM2DSA signing kernels")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, the SM2 encryption kernels, the SM2DSA or the bign signing kernels")
     ap.add_argument("--kernels", help="default: the data-independent kernels of the unit")
     ap.add_argument("--must-flag", default="", help="kernels of the unit that must be reported (comma-separated)")
     ap.add_argument("--asm", help="check an existing .s file instead of compiling")

@@ -17,6 +17,10 @@ much as inputs can.
                                                 same run (profiles/sm2sign/rates.txt).  These calls have host-pointer forms only: their
                                                 wall time includes the PCIe staging, and so does the yardstick's (its host-pointer
                                                 form), which is timed again with reused and with page-locked arrays
+    python tools/gpu_sign_rates.py --bign       bign signing (ecgpu_bign_sign_batch / _sign_prehash_batch / _sign_msg_batch): the rates part and the
+                                                trace part for the three forms on bign256, beside bign256's ecgpu_batch_mul_base_ct of
+                                                the same run (profiles/bignsign/rates.txt), host-pointer calls like --sm2.  The trace
+                                                part ends with the share of each call spent in k_bign_genk beside its k_fixed_base_ct
     python tools/gpu_sign_rates.py --child FORM CURVE CLASS LOG2N     (internal) one call
 
 Every part after the first starts GPU processes of its own.  The first child that does not exit with status 0 ends the whole
@@ -42,6 +46,8 @@ FORMS = ("sign", "rfc6979", "msg", "schnorr")
 SM2_CURVES = {"sm2": 3}
 SM2_FORMS = ("sm2_sign", "sm2_rfc6979", "sm2_msg")
 SM2_DISTID = b"1234567812345678"
+BIGN_CURVES = {"bign256": 11}
+BIGN_FORMS = ("bign_sign", "bign_prehash", "bign_msg")
 CLASSES = ("zeros", "ones", "random", "nm1", "invalid")
 CT_KERNELS = ("k_sign_nonce_load", "k_rfc6979_first", "k_ecdsa_sign_finish", "k_schnorr_nonce", "k_schnorr_sign_finish",
               "k_fixed_base_ct")
@@ -144,6 +150,30 @@ class Sm2Host:
         }
 
 
+class BignHost:
+    """The bign signing forms and their yardstick on n elements in host memory (host-pointer forms only, as for SM2DSA).  Records are
+    little-endian; the top bit of every key, nonce and prehash is cleared, which keeps them below q."""
+
+    def __init__(self, ecgpu, eng, n):
+        self.eng, self.n = eng, n
+        bign = BIGN_CURVES["bign256"]
+
+        def rec(seed, width=32):
+            a = np.random.default_rng(seed).integers(0, 256, n * width, dtype=np.uint8)
+            if width == 32:
+                a[31::32] &= 0x7F
+                a[0::32] |= 1
+            return a
+        self.d, self.k, self.h, self.msgs = rec(0x5161), rec(0x5162), rec(0x5163), rec(0x5164, MSG_LEN + 1)[:n * MSG_LEN]
+        self.xy, self.inf, self.sig, self.ok = (np.zeros(n * w, np.uint8) for w in (64, 1, 48, 1))
+        self.calls = {
+            "ecgpu_batch_mul_base_ct (bign256)": lambda: eng.mul_by_generator(bign, self.d, out=self.xy, inf=self.inf, constant_time=True),
+            "bign_sign": lambda: eng.bign_sign(self.d, self.k, self.h, out=self.sig, ok=self.ok),
+            "bign_prehash": lambda: eng.bign_sign_prehash(self.d, self.h, out=self.sig, ok=self.ok),
+            "bign_msg": lambda: eng.bign_sign_msg(self.d, self.msgs, MSG_LEN, out=self.sig, ok=self.ok),
+        }
+
+
 def timed(fn):
     t0 = time.perf_counter()
     out = fn()                                             # (a host-pointer call returns after its last copy has arrived)
@@ -196,16 +226,44 @@ def sm2_rates(rounds=5):
     eng.close()
 
 
+def bign_rates(rounds=5):
+    """the four host-pointer calls alternating inside a round, median (min .. max) over the rounds after a warm-up round"""
+    ecgpu, eng = engine()
+    n = 1 << 20
+    h = BignHost(ecgpu, eng, n)
+    print("bign signing, 2^20 elements in pageable host memory (host-pointer calls: PCIe staging included, there is no other form),")
+    print("one process, the output arrays reused from call to call;")
+    print("median of %d rounds after one warm-up round, the calls alternating inside a round; ms per call (min .. max)" % rounds)
+    times = {name: [] for name in h.calls}
+    signed = {}
+    for rnd in range(rounds + 1):
+        for name, fn in h.calls.items():
+            ms, out = timed(fn)
+            if rnd:
+                times[name].append(ms)
+            if name.startswith("bign_"):
+                signed[name] = int(out[1].sum())
+    for name, v in times.items():
+        med = statistics.median(v)
+        print("  %-34s %9.2f ms  (%8.2f .. %8.2f)   %6.2f M/s%s" % (name, med, min(v), max(v), n / med / 1e3,
+                                                                   ", %d signed" % signed[name] if name in signed else ""), flush=True)
+    eng.close()
+
+
 def child(form, curve, cls, lg):
     """form "all": every form of the curve once (the counter runs); otherwise the one form twice (the second call is the warm one)"""
     ecgpu, eng = engine()
-    cid = dict(CURVES, **SM2_CURVES)[curve]
+    cid = dict(CURVES, **SM2_CURVES, **BIGN_CURVES)[curve]
     if form == "all":
         for f in FORMS:
             if f != "schnorr" or cid == 0:
                 Call(ecgpu, eng, f, cid, 1 << lg, cls).run()
     elif form in SM2_FORMS:
         h = Sm2Host(ecgpu, eng, 1 << lg, cls)
+        h.calls[form]()
+        h.calls[form]()
+    elif form in BIGN_FORMS:
+        h = BignHost(ecgpu, eng, 1 << lg)
         h.calls[form]()
         h.calls[form]()
     else:
@@ -256,6 +314,10 @@ def trace(curves=CURVES, forms=FORMS):
             for row in rows[:8]:
                 print("      %-44s calls %3s  %9.3f ms  %5.1f %%" % (short(row["Name"])[:44], row["Calls"], float(row["TotalDurationNs"]) / 1e6,
                                                                    100 * float(row["TotalDurationNs"]) / tot))
+            if form in BIGN_FORMS:               # what the generator costs beside the multiplication of the same run
+                ms = lambda kernel: sum(float(row["TotalDurationNs"]) for row in rows if short(row["Name"]).startswith(kernel + "<")) / 1e6
+                print("      k_bign_genk %.3f ms = %.1f %% of the call's kernels, beside k_fixed_base_ct %.3f ms" % (
+                    ms("k_bign_genk"), 100 * ms("k_bign_genk") * 1e6 / tot, ms("k_fixed_base_ct")))
             sys.stdout.flush()
 
 
@@ -301,12 +363,15 @@ def pmc():
 def main():
     if len(sys.argv) > 5 and sys.argv[1] == "--child":
         return child(sys.argv[2], sys.argv[3], sys.argv[4], int(sys.argv[5]))
-    parts = [a for a in sys.argv[1:] if a in ("--rates", "--trace", "--pmc", "--sm2")] or ["--rates", "--trace", "--pmc"]
+    parts = [a for a in sys.argv[1:] if a in ("--rates", "--trace", "--pmc", "--sm2", "--bign")] or ["--rates", "--trace", "--pmc"]
     bad = 0
     try:
         if "--sm2" in parts:
             sm2_rates()
             trace(SM2_CURVES, SM2_FORMS)
+        if "--bign" in parts:
+            bign_rates()
+            trace(BIGN_CURVES, BIGN_FORMS)
         if "--rates" in parts:
             rates()                      # (in this process: an exception or a fault here ends the script by itself)
         if "--trace" in parts:
