@@ -71,7 +71,11 @@ ABI_SYMBOLS = [
     "ecgpu_sm2_pke_encrypt_batch", "ecgpu_sm2_pke_decrypt_batch",
     "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch", "ecgpu_selftest_sign_finish",
     "ecgpu_bign_sign_batch", "ecgpu_bign_sign_prehash_batch", "ecgpu_bign_sign_msg_batch", "ecgpu_selftest_bign_genk",
+    "ecgpu_x448_batch", "ecgpu_x448_unchecked_batch", "ecgpu_x448_base_batch", "ecgpu_selftest_fe448",
 ]
+X448_BYTES = 56
+# the ops of Engine.selftest_fe448 (csrc/ecgpu_x448.h)
+FE448_MUL, FE448_SQR, FE448_ADD, FE448_SUB, FE448_MUL_SMALL, FE448_CARRY, FE448_CANON, FE448_INVERT, FE448_BYTES = range(9)
 SIGN_SCHEME_BIGN = 4
 TABLE_ADAPTIVE, TABLE_EAGER = 0, 1
 EXCHANGE_PEER, EXCHANGE_RCCL = 1, 2
@@ -658,6 +662,59 @@ class Engine:
         self._chk(self._lib.ecgpu_bign_sign_msg_batch(self._ctx, _hp(dd), _hp(mm), ctypes.c_size_t(msg_len), ctypes.c_size_t(n), _hp(sig),
                                                       _hp(ok)))
         return sig, ok
+
+    # ---- X448 (RFC 7748 over Curve448): scalars and results are secrets; every record is 56 little-endian bytes, no curve id ----
+    def _x448_out(self, n, out):
+        out = np.zeros(n * X448_BYTES, np.uint8) if out is None else out
+        if out.dtype != np.uint8 or not out.flags.c_contiguous or out.size < n * X448_BYTES:
+            raise EcgpuError(ERR_ARG, "output buffer must be contiguous uint8 of at least %d bytes" % (n * X448_BYTES))
+        return out
+
+    def x448(self, scalars, points, out=None, ok=None):
+        """`x448::x448(scalar, point)` per element (equally `PublicKey::from_bytes` + `diffie_hellman`): scalars, points n*56 bytes;
+        the scalars are clamped on the device.  Returns (out uint8[n*56], ok uint8[n]): ok = 0 and a zero record exactly where the
+        point's BYTES are 0, 1 or p - 1; a product at infinity (the aliases p and p + 1) is the zero record with ok = 1."""
+        kk, uu = _host(scalars), _host(points)
+        n = kk.size // X448_BYTES
+        _need("scalars", kk, n * X448_BYTES); _need("points", uu, n * X448_BYTES)
+        out = self._x448_out(n, out)
+        ok = np.zeros(n, np.uint8) if ok is None else ok
+        if ok.dtype != np.uint8 or not ok.flags.c_contiguous or ok.size < n:
+            raise EcgpuError(ERR_ARG, "ok must be contiguous uint8 of at least %d bytes" % n)
+        self._chk(self._lib.ecgpu_x448_batch(self._ctx, _hp(kk), _hp(uu), ctypes.c_size_t(n), _hp(out), _hp(ok)))
+        return out, ok
+
+    def x448_unchecked(self, scalars, points, out=None):
+        """`x448::x448_unchecked` per element: as x448 without the low-order test; returns out uint8[n*56]."""
+        kk, uu = _host(scalars), _host(points)
+        n = kk.size // X448_BYTES
+        _need("scalars", kk, n * X448_BYTES); _need("points", uu, n * X448_BYTES)
+        out = self._x448_out(n, out)
+        self._chk(self._lib.ecgpu_x448_unchecked_batch(self._ctx, _hp(kk), _hp(uu), ctypes.c_size_t(n), _hp(out)))
+        return out
+
+    def x448_public_keys(self, scalars, out=None):
+        """`PublicKey::from(&EphemeralSecret)` per element: clamp, then the ladder on u = 5; returns out uint8[n*56]."""
+        kk = _host(scalars)
+        n = kk.size // X448_BYTES
+        _need("scalars", kk, n * X448_BYTES)
+        out = self._x448_out(n, out)
+        self._chk(self._lib.ecgpu_x448_base_batch(self._ctx, _hp(kk), ctypes.c_size_t(n), _hp(out)))
+        return out
+
+    def selftest_fe448(self, op, a, b=None):
+        """One op of csrc/ecgpu_fe448.h on raw limbs (test infrastructure): a, b and the result are uint32 arrays of n records of 16
+        limbs, taken and returned as they are (FE448_* above; FE448_BYTES reads words 0..13 of a as the 56-byte record)."""
+        A = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
+        B = None if b is None else np.ascontiguousarray(b, dtype=np.uint32).reshape(-1)
+        n = A.size // 16
+        _need("a", A.view(np.uint8), n * 64)
+        if B is not None:
+            _need("b", B.view(np.uint8), n * 64)
+        out = np.zeros(n * 16, np.uint32)
+        self._chk(self._lib.ecgpu_selftest_fe448(self._ctx, int(op), _hp(A.view(np.uint8)), _hp(None if B is None else B.view(np.uint8)),
+                                                 ctypes.c_size_t(n), _hp(out.view(np.uint8))))
+        return out.reshape(n, 16)
 
     def selftest_bign_genk(self, d, h, bound):
         """The generator kernels of bign signing with `bound` (32 little-endian bytes) in place of q (test infrastructure): returns

@@ -22,6 +22,7 @@
 #include "ecgpu_hash.h"
 #include "ecgpu_knobs.h"
 #include "ecgpu_recode.h"
+#include "ecgpu_x448.h"
 
 using namespace ecgpu;
 
@@ -842,6 +843,19 @@ int bign_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* 
     return call.done();
 }
 
+// ---- X448 (ecgpu_x448.h): one kernel from the records to the records; mode: X448_CHECKED / X448_UNCHECKED / X448_BASE ----------
+// The ladder state never leaves the registers, so there is no scratch to reserve and none to wipe: what is secret outside the kernel
+// are the staged scalars and the staged results, which the host-pointer entry points mark.  There is no public `_dev` form yet.
+int x448_dev(ecgpu_ctx* ctx, int mode, const void* d_k, const void* d_u, size_t n, void* d_out, void* d_ok) {
+    if (n == 0) return ECGPU_OK;
+    DevCall call(ctx, 0, {});
+    if (call.rc != ECGPU_OK) return call.rc;
+    call.mark(0);
+    launch_x448(ctx->stream, mode, (const uint8_t*)d_k, (const uint8_t*)d_u, n, (uint8_t*)d_out, (uint8_t*)d_ok);
+    call.mark(1);
+    return call.done(SPANS_NO_NORMALIZE);
+}
+
 // ---- SM2 public-key encryption (ecgpu_pke.h): the frame and the steps of ecdsa_sign_dev ----------------------------------------
 // seal (encrypt): d_scalar = k, d_point = P_B, d_in = M; C1 = k G is normalised straight into the caller's array (a public point),
 // (x2, y2) = k P_B into ec_xy, k_pke_seal writes C2 = d_out, C3 = d_c3 and ok (and zeroes the C1 of an element without a verdict).
@@ -1451,6 +1465,11 @@ struct HostCall {
     HostCall(ecgpu_ctx* c, const char* fn_, int curve)
         : ctx(c), fn(fn_), rc(check_ctx(c) ? ECGPU_OK : ECGPU_ERR_ARG), sync(rc == ECGPU_OK ? c : nullptr), L(ecgpu_field_bytes(curve)) {
         if (rc == ECGPU_OK) rc = sync.rc != ECGPU_OK ? sync.rc : L ? (int)ECGPU_OK : curve_error(ctx, fn);
+    }
+    // a call that takes no curve (X448): the same early returns without the curve's
+    HostCall(ecgpu_ctx* c, const char* fn_)
+        : ctx(c), fn(fn_), rc(check_ctx(c) ? ECGPU_OK : ECGPU_ERR_ARG), sync(rc == ECGPU_OK ? c : nullptr), L(0) {
+        if (rc == ECGPU_OK) rc = sync.rc;
     }
     bool bad(bool args_bad) {
         if (rc == ECGPU_OK && args_bad) rc = arg_error(ctx, fn);
@@ -2808,6 +2827,32 @@ int ecgpu_bign_sign_msg_batch(ecgpu_ctx* ctx, const uint8_t* d, const uint8_t* m
                   });
 }
 
+// ---- X448: scalars and results (shared secrets, and public keys all the same) are staged as secrets; points and verdicts are public ----
+// (host-pointer forms only: x448_dev is internal, every chunk reaches it through `staged`; no curve argument)
+int ecgpu_x448_batch(ecgpu_ctx* ctx, const uint8_t* scalars, const uint8_t* points_u, size_t n, uint8_t* out_u, uint8_t* ok) {
+    HostCall c(ctx, __func__);
+    if (c.bad(n && (!scalars || !points_u || !out_u || !ok))) return c.rc;
+    if (n == 0) return ECGPU_OK;
+    return staged(ctx, n, {{scalars, &ctx->in0, 56, SECRET}, {points_u, &ctx->in1, 56}}, {{out_u, &ctx->out0, 56, SECRET}, {ok, &ctx->out1, 1}},
+                  [&](auto in, auto out, size_t m) { return x448_dev(ctx, X448_CHECKED, in[0], in[1], m, out[0], out[1]); });
+}
+
+int ecgpu_x448_unchecked_batch(ecgpu_ctx* ctx, const uint8_t* scalars, const uint8_t* points_u, size_t n, uint8_t* out_u) {
+    HostCall c(ctx, __func__);
+    if (c.bad(n && (!scalars || !points_u || !out_u))) return c.rc;
+    if (n == 0) return ECGPU_OK;
+    return staged(ctx, n, {{scalars, &ctx->in0, 56, SECRET}, {points_u, &ctx->in1, 56}}, {{out_u, &ctx->out0, 56, SECRET}},
+                  [&](auto in, auto out, size_t m) { return x448_dev(ctx, X448_UNCHECKED, in[0], in[1], m, out[0], nullptr); });
+}
+
+int ecgpu_x448_base_batch(ecgpu_ctx* ctx, const uint8_t* scalars, size_t n, uint8_t* out_u) {
+    HostCall c(ctx, __func__);
+    if (c.bad(n && (!scalars || !out_u))) return c.rc;
+    if (n == 0) return ECGPU_OK;
+    return staged(ctx, n, {{scalars, &ctx->in0, 56, SECRET}}, {{out_u, &ctx->out0, 56, SECRET}},
+                  [&](auto in, auto out, size_t m) { return x448_dev(ctx, X448_BASE, in[0], nullptr, m, out[0], nullptr); });
+}
+
 // ---- SM2 public-key encryption: k, d and the messages are staged as secrets; C1, C2 and C3 are public ----
 // (host-pointer forms only: sm2_pke_dev is internal, every chunk reaches it through `staged`)
 int ecgpu_sm2_pke_encrypt_batch(ecgpu_ctx* ctx, const uint8_t* pk_xy, const uint8_t* k, const uint8_t* msgs, size_t msg_len, size_t n,
@@ -2977,6 +3022,21 @@ int ecgpu_selftest_point_raw(ecgpu_ctx* ctx, int curve, int op, const uint8_t* p
             return (int)ECGPU_OK;
         });
         return rc != ECGPU_OK ? rc : finish(ctx);
+    }, STAGE_WHOLE);
+}
+
+// One op of csrc/ecgpu_fe448.h on raw limbs (test infrastructure: tests/fe448_vectors.py).  a, b, out: 16 little-endian 32-bit
+// words per element, so that lazy representatives can be handed in; b may be NULL for the ops of one operand (it reads as zero).
+// Ops: 0 mul, 1 sqr, 2 add, 3 sub, 4 mul_small(39082), 5 carry, 6 canon, 7 invert, 8 from_bytes -> to_bytes (ecgpu_x448.h).
+int ecgpu_selftest_fe448(ecgpu_ctx* ctx, int op, const uint8_t* a, const uint8_t* b, size_t n, uint8_t* out) {
+    HostCall c(ctx, __func__);
+    if (c.bad(op < 0 || op >= FE448_OPS || (n && (!a || !out)))) return c.rc;
+    if (n == 0) return ECGPU_OK;
+    return staged(ctx, n, {{a, &ctx->in0, 64}, {b, &ctx->in1, 64}}, {{out, &ctx->out0, 64}}, [&](auto in, auto o, size_t m) -> int {
+        int rc = reset_status(ctx);
+        if (rc != ECGPU_OK) return rc;
+        launch_selftest_fe448(ctx->stream, op, (const uint32_t*)in[0], (const uint32_t*)in[1], m, (uint32_t*)o[0]);
+        return finish(ctx);
     }, STAGE_WHOLE);
 }
 

@@ -199,6 +199,10 @@ void launch_sm2dsa_finish(hipStream_t s, const uint8_t* e, const uint8_t* r_xy, 
                           const uint8_t* valid, size_t n, uint8_t* ok);
 void launch_sm2dsa_hash_msg(hipStream_t s, const uint8_t* distid, size_t distid_len, const uint8_t* q_xy, const uint8_t* msgs,
                             size_t msg_len, const uint8_t* sigs, size_t n, uint8_t* e_out, uint8_t* r_out, uint8_t* s_out);
+// X448 (ecgpu_x448.h, ecgpu_x448.hip): mode 0 = checked (ok: n verdict bytes), 1 = unchecked, 2 = the base form (points unused);
+// 56-byte records.  The fe448 self-test: one op on records of 16 raw limbs, b may be null
+void launch_x448(hipStream_t s, int mode, const uint8_t* scalars, const uint8_t* points, size_t n, uint8_t* out, uint8_t* ok);
+void launch_selftest_fe448(hipStream_t s, int op, const uint32_t* a, const uint32_t* b, size_t n, uint32_t* out);
 void launch_k256_glv(hipStream_t s, const uint8_t* scalars, size_t n, uint8_t* r1, uint8_t* r2, int* status);
 void launch_valu_probe(hipStream_t s, int which, uint32_t* out, int blocks, int iters);
 void launch_isa_probe(hipStream_t s, int which, uint32_t* out, int blocks, int iters);

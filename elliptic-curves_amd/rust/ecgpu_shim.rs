@@ -661,6 +661,52 @@ pub mod gpu {
         Some(sig.chunks(48).zip(ok).map(|(s, f)| if f != 0 { Some(s.try_into().unwrap()) } else { None }).collect())
     }
 
+    /// Batch form of `x448::x448(scalar, point)` (x448/src/lib.rs:152-156), which is also `PublicKey::from_bytes` followed by
+    /// `EphemeralSecret::diffie_hellman`: 56-byte records, the scalars clamped on the device (`ecgpu_x448_batch`).  `None` per
+    /// element exactly where the point's bytes are one of the three low-order records.  The wire copy of the scalars and the
+    /// results are wiped here, the device side by the library.
+    pub fn x448_batch(scalars: &[Zeroizing<[u8; 56]>], points: &[[u8; 56]]) -> Option<Vec<Option<Zeroizing<[u8; 56]>>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = scalars.len();
+        assert!(points.len() == n);
+        let mut k = Zeroizing::new(Vec::with_capacity(56 * n));
+        for s in scalars {
+            k.extend_from_slice(&s[..]);
+        }
+        let (mut out, mut ok) = (Zeroizing::new(vec![0u8; 56 * n]), vec![0u8; n]);
+        check(unsafe { ecgpu_x448_batch(eng.0, k.as_ptr(), points.as_ptr() as *const u8, n, out.as_mut_ptr(), ok.as_mut_ptr()) })?;
+        Some(out.chunks(56).zip(ok).map(|(s, f)| if f != 0 { Some(Zeroizing::new(s.try_into().unwrap())) } else { None }).collect())
+    }
+
+    /// Batch form of `x448::x448_unchecked` (x448/src/lib.rs:159-163), and of `diffie_hellman` on `PublicKey::from_bytes_unchecked`:
+    /// the same without the low-order test (`ecgpu_x448_unchecked_batch`); a low-order point gives the zero record.
+    pub fn x448_unchecked_batch(scalars: &[Zeroizing<[u8; 56]>], points: &[[u8; 56]]) -> Option<Vec<Zeroizing<[u8; 56]>>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = scalars.len();
+        assert!(points.len() == n);
+        let mut k = Zeroizing::new(Vec::with_capacity(56 * n));
+        for s in scalars {
+            k.extend_from_slice(&s[..]);
+        }
+        let mut out = Zeroizing::new(vec![0u8; 56 * n]);
+        check(unsafe { ecgpu_x448_unchecked_batch(eng.0, k.as_ptr(), points.as_ptr() as *const u8, n, out.as_mut_ptr()) })?;
+        Some(out.chunks(56).map(|s| Zeroizing::new(s.try_into().unwrap())).collect())
+    }
+
+    /// Batch form of `PublicKey::from(&EphemeralSecret)` (x448/src/lib.rs:25-31): clamp, then the ladder on the generator u = 5
+    /// (`ecgpu_x448_base_batch`).  The wire copy of the scalars is wiped here.
+    pub fn x448_public_keys_batch(scalars: &[Zeroizing<[u8; 56]>]) -> Option<Vec<[u8; 56]>> {
+        let eng = ENGINE.as_ref()?.lock().ok()?;
+        let n = scalars.len();
+        let mut k = Zeroizing::new(Vec::with_capacity(56 * n));
+        for s in scalars {
+            k.extend_from_slice(&s[..]);
+        }
+        let mut out = vec![0u8; 56 * n];
+        check(unsafe { ecgpu_x448_base_batch(eng.0, k.as_ptr(), n, out.as_mut_ptr()) })?;
+        Some(out.chunks(56).map(|s| s.try_into().unwrap()).collect())
+    }
+
     /// Batch form of `hash2curve::GroupDigest::hash_from_bytes(&[msg], &[dst])` (hash2curve/src/group_digest.rs) for the curves
     /// with a suite on the device (k256, p256, p384): `msgs` holds `n` messages of `msg_len` bytes each, `dst` is the one domain
     /// separation tag of the batch (not empty: `Domain::xmd` refuses that, and so does the library).

@@ -724,6 +724,22 @@ unsafe extern "C" {
         out_sig: *mut u8,
         ok: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_x448_batch(
+        ctx: *mut EcgpuCtx,
+        scalars: *const u8,
+        points_u: *const u8,
+        n: usize,
+        out_u: *mut u8,
+        ok: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_x448_unchecked_batch(
+        ctx: *mut EcgpuCtx,
+        scalars: *const u8,
+        points_u: *const u8,
+        n: usize,
+        out_u: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_x448_base_batch(ctx: *mut EcgpuCtx, scalars: *const u8, n: usize, out_u: *mut u8) -> c_int;
     pub fn ecgpu_batch_mul_ct_xyz(
         ctx: *mut EcgpuCtx,
         curve: c_int,
@@ -992,6 +1008,14 @@ unsafe extern "C" {
         op: c_int,
         p: *const u8,
         q: *const u8,
+        n: usize,
+        out: *mut u8,
+    ) -> c_int;
+    pub fn ecgpu_selftest_fe448(
+        ctx: *mut EcgpuCtx,
+        op: c_int,
+        a: *const u8,
+        b: *const u8,
         n: usize,
         out: *mut u8,
     ) -> c_int;

@@ -676,6 +676,38 @@ int ecgpu_bign_sign_prehash_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_
 int ecgpu_bign_sign_msg_batch(ecgpu_ctx *ctx, const uint8_t *d, const uint8_t *msgs, size_t msg_len, size_t n, uint8_t *out_sig,
                               uint8_t *ok);
 
+/* ---- batch X448 (RFC 7748): Diffie-Hellman over Curve448, the `x448` crate --------------------------------------------------
+ * Curve448 is not a short-Weierstrass curve: these calls take no `curve` argument, there is no id for it in the enum above, and no
+ * generic entry point knows it.  Every record — scalar, u-coordinate, result — is 56 bytes, little-endian; ok: one byte per element.
+ * The clamp: every scalar is clamped on the device, bytes[0] &= 252 and bytes[55] |= 128 (x448/src/lib.rs:122-126), and the clamped
+ *   448-bit integer is used as it is, never reduced modulo the group order.  There is no unclamped form.
+ * The point: any 56 bytes, taken modulo p = 2^448 - 2^224 - 1 (`FieldElement::from_bytes`, ed448-goldilocks/src/field/element.rs:370-372):
+ *   u in [p, 2^448) is legal input.  Points on the twist go through like any other.
+ * The result: U W^-1 of the Montgomery ladder (ed448-goldilocks/src/montgomery.rs:83-110,168-204) with 0^-1 = 0, canonical.  A
+ *   result at infinity is the zero record: 56 zero bytes, and it is NOT an error of the multiplication.
+ * The low-order rule is byte-wise: the checked form refuses an element exactly when the point's BYTES equal one of the three
+ *   low-order records LOW_A (0), LOW_B (1), LOW_C (p - 1) (montgomery.rs:23-42,137-139); such an element gets ok[i] = 0 and the zero
+ *   record, and its neighbours are untouched.  The two non-canonical aliases p (= 0) and p + 1 (= 1) are NOT refused: they give the
+ *   zero record with ok[i] = 1, as the reference does.
+ * Secrecy: scalars and results are secret (a shared secret is a key).  In k_x448_ladder no branch and no address depends on scalar
+ *   bytes, ladder state or results (tools/ct_isa_check.py --unit x448; tests/test_x448_isa.py); the ladder state lives in registers
+ *   only.  The staged copies of the scalars and of the results are zeroed behind the last kernel in stream order, and ecgpu_wipe
+ *   covers the same buffers.  The caller's own arrays are the caller's to wipe.
+ * n = 0 succeeds and touches nothing; a NULL array with n > 0 is ECGPU_ERR_ARG; without a context every call is ECGPU_ERR_ARG.
+ *
+ * ecgpu_x448_batch - `x448::x448(scalar, point)` (lib.rs:152-156), and equally `PublicKey::from_bytes` followed by
+ *   `EphemeralSecret::diffie_hellman`: `None` there is ok[i] = 0 here.
+ * ecgpu_x448_unchecked_batch - `x448::x448_unchecked` (lib.rs:159-163), and `diffie_hellman` on `from_bytes_unchecked`: the same
+ *   without the low-order test; the three low-order records give the zero record.
+ * ecgpu_x448_base_batch - `PublicKey::from(&EphemeralSecret)` (lib.rs:25-31): clamp, then the ladder on `GENERATOR` (u = 5), with
+ *   the product by u as a product by a small constant.
+ * Out of scope: a table-driven fixed base, Ed448 / Decaf448, ecgpu_group_* forms, the C++ mirror.
+ * Host-pointer forms only, no `_dev` name yet.  From 2^19 elements a call is pipelined in pieces like every batch call; on an
+ * asynchronous context a call first waits for the queued work and runs synchronously, as every host-pointer call does. */
+int ecgpu_x448_batch(ecgpu_ctx *ctx, const uint8_t *scalars, const uint8_t *points_u, size_t n, uint8_t *out_u, uint8_t *ok);
+int ecgpu_x448_unchecked_batch(ecgpu_ctx *ctx, const uint8_t *scalars, const uint8_t *points_u, size_t n, uint8_t *out_u);
+int ecgpu_x448_base_batch(ecgpu_ctx *ctx, const uint8_t *scalars, size_t n, uint8_t *out_u);
+
 /* The same two with projective points: point i is the record X || Y || Z of the wire format above (3L bytes, no flag array),
  * as the reference's `Mul<Scalar>` and `lincomb` take a `ProjectivePoint`.  For every input the results and the return code
  * are those of `to_affine` applied to each record followed by ecgpu_batch_mul_ct / ecgpu_lincomb_ct: X, Y or Z >= p, and a
@@ -892,6 +924,19 @@ int ecgpu_selftest_field(ecgpu_ctx *ctx, int curve, int op, const uint8_t *a, co
 int ecgpu_selftest_point(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p_xy, const uint8_t *p_inf, const uint8_t *q_xy,
                          const uint8_t *q_inf, size_t n, uint8_t *out_xy, uint8_t *out_inf);
 int ecgpu_selftest_point_raw(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p, const uint8_t *q, size_t n, uint8_t *out);
+
+/* Test infrastructure: one op of the Goldilocks field (csrc/ecgpu_fe448.h, p = 2^448 - 2^224 - 1) on RAW limbs, modelled on
+ * ecgpu_selftest_point_raw: a, b and out are records of 16 little-endian 32-bit words, the 28-bit limbs as they are, so that lazy
+ * representatives can be handed in; nothing is converted or range-checked.  b may be NULL (zeros).  Any n; no curve argument.
+ *     op  operation                    limbs accepted                 op  operation                    limbs accepted
+ *      0  mul(a, b)                    <= 2 T each                     5  carry(a)                     any 32-bit words
+ *      1  sqr(a)                       <= 2 T                          6  canon(a): [0, p)             <= 15 T
+ *      2  add(a, b), lazy sum          <= T each                       7  invert(a) = a^(p-2), 0 -> 0  <= T
+ *      3  sub(a, b)                    <= 2 T each                     8  from_bytes -> to_bytes: words 0..13 of a are the
+ *      4  mul_small(a, 39082)          <= 2 T                             56-byte record; out words 14, 15 are zero
+ *   T = 2^28 + 2^8, the limb bound of a tight element.  Beyond what an op accepts the result means nothing (the device does not
+ *   check; the bounds-checking host build of tests/hostcheck_x448 traps).  ECGPU_ERR_ARG: unknown op or a missing array. */
+int ecgpu_selftest_fe448(ecgpu_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
 
 /* Test infrastructure: the finish kernels of the signing entry points on stages the CALLER supplies, so that a test can hand them
  * what no input of the pipelines produces (x(R) in [n, p), R at infinity, a cleared nonce flag beside a valid k, a Schnorr nonce that

@@ -25,6 +25,10 @@ generator's state and S0 are all loaded records or derived from them; the bound 
 generator's S-box lookups are computed (Belt::CtSbox), so k_bign_genk holds no data-dependent address.  The two kernels that MUST be
 reported show that the analysis sees what it is there for in this unit: k_bign_genk_retry loops on the rejected candidates, and
 k_bign_sign_s0 (public inputs) indexes the S-box table in LDS by loaded bytes.
+    python tools/ct_isa_check.py --unit x448 --curve K256Params
+the X448 kernels (csrc/ecgpu_x448.h, translation unit ecgpu_x448.hip, built once: the curve name is ignored): scalars, points, the
+ladder state and the results are all loaded records or derived from them; n is a kernel argument.  The three instantiations of
+k_x448_ladder (checked, unchecked, base) are checked; the low-order verdict of the checked one is computed without a branch.
 
 How: the translation unit is compiled to assembly (hipcc -S --offload-device-only; no GPU needed) and every selected kernel
 goes through a forward taint analysis over its control-flow graph (register-precise, iterated to a fixed point):
@@ -393,6 +397,8 @@ UNITS = {
     # (names are matched inside the mangled ones: the `I` that opens the template arguments keeps k_bign_genk_retry, which is
     # variable-time on purpose, out of the default list)
     "bignsign": ("ecgpu_inst_sign.hip", "k_bign_genkI,k_bign_sign_finish,k_sign_nonce_load"),
+    # (one name, three kernels: the checked, unchecked and base instantiations of the ladder; the unit ignores -DECGPU_CURVE)
+    "x448": ("ecgpu_x448.hip", "k_x448_ladder"),
 }
 
 
@@ -425,7 +431,7 @@ def check(asm, wanted, verbose=False, seen_names=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--curve", action="append")
-    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, the SM2 encryption kernels, the SM2DSA or the bign signing kernels")
+    ap.add_argument("--unit", choices=sorted(UNITS), default="ct", help="translation unit: the _ct entry points, the signing kernels, the hash-to-curve kernels, the SM2 encryption kernels, the SM2DSA or the bign signing kernels, the X448 kernels")
     ap.add_argument("--kernels", help="default: the data-independent kernels of the unit")
     ap.add_argument("--must-flag", default="", help="kernels of the unit that must be reported (comma-separated)")
     ap.add_argument("--asm", help="check an existing .s file instead of compiling")

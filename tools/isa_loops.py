@@ -7,6 +7,7 @@ the inversion in k_normalize).  Compiles the kernel group's translation unit wit
     python tools/isa_loops.py msm K256Params k_msm_combine
     python tools/isa_loops.py msm K256Params k_msm_accumulate -DECGPU_K256_ASM_REDUCE=0
     python tools/isa_loops.py base K256Params k_normalizeINS_10K256ParamsELi0E
+    python tools/isa_loops.py x448 K256Params k_x448_ladder
 """
 import collections
 import os
@@ -17,13 +18,15 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "elliptic-curves_amd", "csrc")
+UNITS = {"x448": "ecgpu_x448.hip"}          # groups whose translation unit is built once, not per curve (the curve name is ignored)
 
 
 def loops(group, curve, substr, flags=()):
     with tempfile.TemporaryDirectory() as td:
         out = os.path.join(td, "k.s")
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-DECGPU_CURVE=" + curve, "-S", "--offload-device-only",
-                               "-o", out, os.path.join(CSRC, "ecgpu_inst_%s.hip" % group)] + list(flags), stderr=subprocess.DEVNULL)
+                               "-o", out, os.path.join(CSRC, UNITS.get(group, "ecgpu_inst_%s.hip" % group))] + list(flags),
+                              stderr=subprocess.DEVNULL)
         txt = open(out).read()
     res = []
     for m in re.finditer(r"^(_Z\w+):\s*;[^\n]*\n(.*?)^\.Lfunc_end", txt, re.S | re.M):
