@@ -72,7 +72,11 @@ ABI_SYMBOLS = [
     "ecgpu_sm2dsa_sign_batch", "ecgpu_sm2dsa_sign_rfc6979_batch", "ecgpu_sm2dsa_sign_msg_batch", "ecgpu_selftest_sign_finish",
     "ecgpu_bign_sign_batch", "ecgpu_bign_sign_prehash_batch", "ecgpu_bign_sign_msg_batch", "ecgpu_selftest_bign_genk",
     "ecgpu_x448_batch", "ecgpu_x448_unchecked_batch", "ecgpu_x448_base_batch", "ecgpu_selftest_fe448",
+    "ecgpu_selftest_h2c",
 ]
+# the ops of Engine.selftest_h2c (csrc/ecgpu_h2c.h) and the suites' draw lengths L
+H2C_ST_REDUCE_P, H2C_ST_REDUCE_N, H2C_ST_SSWU, H2C_ST_ISO = range(4)
+H2C_DRAW_BYTES = {K256: 48, P256: 48, P384: 72}
 X448_BYTES = 56
 # the ops of Engine.selftest_fe448 (csrc/ecgpu_x448.h)
 FE448_MUL, FE448_SQR, FE448_ADD, FE448_SUB, FE448_MUL_SMALL, FE448_CARRY, FE448_CANON, FE448_INVERT, FE448_BYTES = range(9)
@@ -889,6 +893,19 @@ class Engine:
         out, inf = np.zeros(n * 2 * L, np.uint8), np.zeros(n, np.uint8)
         self._chk(self._lib.ecgpu_map_to_curve_batch(self._ctx, curve, _hp(uu), int(per_point), ctypes.c_size_t(n), _hp(out), _hp(inf)))
         return out, inf
+
+    def selftest_h2c(self, curve, op, records):
+        """One lane body of csrc/ecgpu_h2c.h on the caller's records (test infrastructure; H2C_ST_* above): ops 0 / 1 reduce records
+        of L = H2C_DRAW_BYTES[curve] bytes mod p / mod n to field-sized records, op 2 maps u to xn || xd || y, op 3 (k256) takes
+        xn || xd || y through the isogeny to X || Y || Z.  Returns the output records as one uint8 array."""
+        F = _field_bytes(curve)
+        rr = _host(records)
+        unit = H2C_DRAW_BYTES.get(curve, F) if op in (H2C_ST_REDUCE_P, H2C_ST_REDUCE_N) else F if op == H2C_ST_SSWU else 3 * F
+        n = rr.size // unit
+        _need("records", rr, n * unit)
+        out = np.zeros(n * (F if op in (H2C_ST_REDUCE_P, H2C_ST_REDUCE_N) else 3 * F), np.uint8)
+        self._chk(self._lib.ecgpu_selftest_h2c(self._ctx, curve, int(op), _hp(rr), ctypes.c_size_t(n), _hp(out)))
+        return out
 
     # ---- SM2 public-key encryption (`sm2::pke`; secret nonces, keys and messages: the uniform-schedule multiplications) ----
     def sm2_pke_encrypt(self, pk_xy, k, msgs, msg_len):

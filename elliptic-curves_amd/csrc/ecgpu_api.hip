@@ -3040,6 +3040,28 @@ int ecgpu_selftest_fe448(ecgpu_ctx* ctx, int op, const uint8_t* a, const uint8_t
     }, STAGE_WHOLE);
 }
 
+// One lane body of csrc/ecgpu_h2c.h on the caller's records (test infrastructure: tests/h2c_vectors.py).  Ops: 0 reduce mod p,
+// 1 reduce mod n (records of L = 48 / 72 bytes in, one wire record out), 2 sswu (u in, xn || xd || y out), 3 the secp256k1 isogeny
+// (xn || xd || y in, X || Y || Z out).  The early returns are those of ecgpu_map_to_curve_batch, the op where it has per_point.
+int ecgpu_selftest_h2c(ecgpu_ctx* ctx, int curve, int op, const uint8_t* in, size_t n, uint8_t* out) {
+    HostCall h(ctx, __func__, curve);
+    if (h.bad(op < 0 || op >= H2C_ST_OPS || (n && (!in || !out)))) return h.rc;
+    if (!h2c_has_suite(curve) || (op == H2C_ST_ISO && curve != ECGPU_K256)) return curve_error(ctx, __func__);
+    if (n == 0) return ECGPU_OK;
+    const size_t draw = (size_t)dispatch(curve, [](auto c) { return h2c_draw_bytes<decltype(c)>(); });
+    const bool reduce = op == H2C_ST_REDUCE_P || op == H2C_ST_REDUCE_N;
+    const size_t in_unit = reduce ? draw : op == H2C_ST_SSWU ? h.L : 3 * h.L, out_unit = reduce ? h.L : 3 * h.L;
+    return staged(ctx, n, {{in, &ctx->in0, in_unit}}, {{out, &ctx->out0, out_unit}}, [&](auto i, auto o, size_t m) -> int {
+        int rc = reset_status(ctx);
+        if (rc != ECGPU_OK) return rc;
+        rc = dispatch(curve, [&](auto c) {
+            launch_selftest_h2c<decltype(c)>(ctx->stream, op, (const uint8_t*)i[0], m, (uint8_t*)o[0]);
+            return (int)ECGPU_OK;
+        });
+        return rc != ECGPU_OK ? rc : finish(ctx);
+    }, STAGE_WHOLE);
+}
+
 // The signing pipelines' finish kernels on stages the caller supplies (test infrastructure: tests/sign_vectors.py).  Nothing is
 // computed before the kernel: flag, affine R and r_inf are what the nonce, fixed-base and normalisation kernels would have left.
 int ecgpu_selftest_sign_finish(ecgpu_ctx* ctx, int curve, int scheme, const uint8_t* d, const uint8_t* k, const uint8_t* flag,

@@ -327,6 +327,7 @@ struct H2cMap {
 #if defined(__HIPCC__)
 
 #include "ecgpu_kernels.h"
+#include "ecgpu_launch.h"
 
 namespace ecgpu {
 
@@ -383,6 +384,62 @@ static __global__ void __launch_bounds__(BLOCK) k_h2c_flags(const uint8_t* __res
     uint32_t f = 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) f |= flags[i];
     if (f) atomicOr(status, (int)f);
+}
+
+// ---- ecgpu_selftest_h2c: one lane body of this file on records the caller supplies (test infrastructure: tests/h2c_vectors.py) ----
+// A kernel of its own: k_h2c_expand and k_h2c_map stay as they are, and this one calls the same functions on what no digest and no
+// map produces.  op (H2C_ST_*, ecgpu_launch.h; an argument of the call, uniform):
+//     0  h2c_reduce_field    L bytes (OKM, big-endian)        ->  the residue mod p as a wire record
+//     1  h2c_reduce_scalar   L bytes                          ->  the residue mod n as a wire record
+//     2  H2cMap::sswu        u, a wire record below p         ->  xn || xd || y, canonical wire records
+//     3  H2cMap::iso_k256    xn || xd || y, wire records      ->  X || Y || Z, canonical wire records (secp256k1 only)
+// Nothing is range-checked: the entry point says what each op accepts.
+template <class C>
+__global__ void __launch_bounds__(BLOCK)
+k_selftest_h2c(int op, const uint8_t* __restrict__ in, size_t n, uint8_t* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if constexpr (H2cSuite<C>::SUPPORTED) {
+        using F = Field<C>;
+        using G = Group<C>;
+        using M = H2cMap<C>;
+        constexpr int N = C::N, WB = WireBytes<C>::value, L = H2cSuite<C>::L;
+        uint32_t w[N];
+        if (op == H2C_ST_REDUCE_P || op == H2C_ST_REDUCE_N) {
+            // the record goes to a private array first, as k_h2c_expand holds its OKM: handed the global pointer, the compiler
+            // merged h2c_piece_words' byte loads into wide ones and its byte extraction left bits of a neighbouring byte in a
+            // word (k256 mod p on gfx950: bits 24, 25 of word 1 came out as byte 40 | byte 42), the defect ecgpu_kernels.h
+            // describes at load_wire
+            uint8_t ub[L];
+#pragma unroll
+            for (int k = 0; k < L; k++) ub[k] = in[i * L + k];
+            if (op == H2C_ST_REDUCE_N) h2c_reduce_scalar<C>(w, ub);
+            else h2c_reduce_field<C>(w, ub);
+            store_wire<C>(out + i * WB, w);
+        } else if (op == H2C_ST_SSWU) {
+            typename M::E e[3];
+            load_wire<C>(w, in + i * WB);
+            M::sswu(&e[0], &e[1], &e[2], w);
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                F::to_canonical(w, G::m(e[j]));
+                store_wire<C>(out + (3 * i + j) * WB, w);
+            }
+        } else if (op == H2C_ST_ISO) {
+            if constexpr (C::ID == CURVE_K256) {
+                typename M::E e[3];
+#pragma unroll
+                for (int j = 0; j < 3; j++) {
+                    load_wire<C>(w, in + (3 * i + j) * WB);
+                    e[j] = F::from_canonical(w).e;
+                }
+                const Proj<C> q = M::iso_k256(e[0], e[1], e[2]);
+                F::to_canonical(w, G::m(q.x)); store_wire<C>(out + (3 * i) * WB, w);
+                F::to_canonical(w, G::m(q.y)); store_wire<C>(out + (3 * i + 1) * WB, w);
+                F::to_canonical(w, G::m(q.z)); store_wire<C>(out + (3 * i + 2) * WB, w);
+            }
+        }
+    }
 }
 
 }  // namespace ecgpu

@@ -24,5 +24,9 @@ template <> void launch_h2c_map<CurveT>(hipStream_t s, const uint8_t* u, int per
     hipLaunchKernelGGL(k_h2c_map<CurveT>, dim3(h2c_grid(n)), dim3(BLOCK), 0, s, u, per_point, n, proj_out, flags);
     hipLaunchKernelGGL(k_h2c_flags, dim3(64), dim3(BLOCK), 0, s, (const uint8_t*)flags, n, status);
 }
+template <> int h2c_draw_bytes<CurveT>() { return H2cSuite<CurveT>::L; }
+template <> void launch_selftest_h2c<CurveT>(hipStream_t s, int op, const uint8_t* in, size_t n, uint8_t* out) {
+    hipLaunchKernelGGL(k_selftest_h2c<CurveT>, dim3(h2c_grid(n)), dim3(BLOCK), 0, s, op, in, n, out);
+}
 
 }  // namespace ecgpu

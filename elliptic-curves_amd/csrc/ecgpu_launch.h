@@ -162,6 +162,10 @@ template <class C> void launch_h2c_expand(hipStream_t s, const uint8_t* msgs, si
 // proj_out[i] = the sum of the maps of per_point (1 or 2) consecutive u records; flags: n verdict bytes, ORed into status
 template <class C> void launch_h2c_map(hipStream_t s, const uint8_t* u, int per_point, size_t n, uint32_t* proj_out, uint8_t* flags,
                                        int* status);
+// the self-test (k_selftest_h2c): one lane body on the caller's records.  h2c_draw_bytes: L of the suite, the record of ops 0 and 1
+enum : int { H2C_ST_REDUCE_P = 0, H2C_ST_REDUCE_N = 1, H2C_ST_SSWU = 2, H2C_ST_ISO = 3, H2C_ST_OPS = 4 };
+template <class C> int h2c_draw_bytes();
+template <class C> void launch_selftest_h2c(hipStream_t s, int op, const uint8_t* in, size_t n, uint8_t* out);
 
 // ---- group "msm": Pippenger pipeline ----
 template <class C> MsmPlan msm_plan(size_t n, int force_c, bool glv);

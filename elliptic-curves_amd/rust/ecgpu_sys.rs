@@ -1019,6 +1019,14 @@ unsafe extern "C" {
         n: usize,
         out: *mut u8,
     ) -> c_int;
+    pub fn ecgpu_selftest_h2c(
+        ctx: *mut EcgpuCtx,
+        curve: c_int,
+        op: c_int,
+        in: *const u8,
+        n: usize,
+        out: *mut u8,
+    ) -> c_int;
     pub fn ecgpu_selftest_sign_finish(
         ctx: *mut EcgpuCtx,
         curve: c_int,

@@ -938,6 +938,22 @@ int ecgpu_selftest_point_raw(ecgpu_ctx *ctx, int curve, int op, const uint8_t *p
  *   check; the bounds-checking host build of tests/hostcheck_x448 traps).  ECGPU_ERR_ARG: unknown op or a missing array. */
 int ecgpu_selftest_fe448(ecgpu_ctx *ctx, int op, const uint8_t *a, const uint8_t *b, size_t n, uint8_t *out);
 
+/* Test infrastructure: one lane body of hash-to-curve (csrc/ecgpu_h2c.h) on records the CALLER supplies, so that a test can hand
+ * the reductions and the map what no digest produces (pieces of all ones, OKM = k m, a final addition that lands on m, a u with
+ * structured limbs, a forged isogeny denominator).  A kernel of its own that calls the functions k_h2c_expand and k_h2c_map call;
+ * the device-side twin of tests/hostcheck_h2c.  Records are big-endian; L = 48 bytes (ECGPU_K256, ECGPU_P256) or 72 (ECGPU_P384)
+ * is the suite's draw length, F = ecgpu_field_bytes(curve).
+ *     op  function             in[i]                                   out[i]
+ *      0  h2c_reduce_field     L bytes, any value                      F bytes: OS2IP(in) mod p
+ *      1  h2c_reduce_scalar    L bytes, any value                      F bytes: OS2IP(in) mod n
+ *      2  H2cMap::sswu         u, F bytes, below p (not checked)       xn || xd || y, 3 F bytes, canonical: the point (xn / xd, y)
+ *                                                                      of the curve the map runs on (E' for secp256k1)
+ *      3  H2cMap::iso_k256     xn || xd || y, 3 F bytes, each below p  X || Y || Z, 3 F bytes, canonical: the image of (xn / xd, y)
+ *                              (need not be on E'; xd = 0 means nothing) under the 3-isogeny; a zero denominator gives (0 : 1 : 0)
+ *   Op 3 exists for ECGPU_K256 only.  ECGPU_ERR_ARG: unknown op, or a NULL array with n > 0; ECGPU_ERR_CURVE: a curve without a
+ *   suite (ECGPU_P521 included), or op 3 on another curve than ECGPU_K256.  n = 0 succeeds and touches nothing. */
+int ecgpu_selftest_h2c(ecgpu_ctx *ctx, int curve, int op, const uint8_t *in, size_t n, uint8_t *out);
+
 /* Test infrastructure: the finish kernels of the signing entry points on stages the CALLER supplies, so that a test can hand them
  * what no input of the pipelines produces (x(R) in [n, p), R at infinity, a cleared nonce flag beside a valid k, a Schnorr nonce that
  * cancels e d').  Nothing runs before the kernel: `flag` is the nonce's verdict byte, r_xy the affine R (x || y) and r_inf its

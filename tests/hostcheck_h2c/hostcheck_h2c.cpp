@@ -56,6 +56,44 @@ int hh_expand(int curve, const uint8_t* msgs, size_t msg_len, size_t n, const ui
     });
 }
 
+// the two reductions alone on n records of L bytes the caller chose (hh_expand reaches them only behind the hash): out[i] = the
+// residue mod p (to_scalar == 0) or mod n as a wire record — op 0 / 1 of ecgpu_selftest_h2c
+int hh_reduce(int curve, int to_scalar, const uint8_t* okm, size_t n, uint8_t* out) {
+    return dispatch(curve, [&](auto c) -> int {
+        using C = decltype(c);
+        constexpr int N = C::N, WB = WireBytes<C>::value, L = H2cSuite<C>::L;
+        for (size_t i = 0; i < n; i++) {
+            uint32_t w[N];
+            if (to_scalar) h2c_reduce_scalar<C>(w, okm + i * L);
+            else h2c_reduce_field<C>(w, okm + i * L);
+            store_be_wire<C>(out + i * WB, w);
+        }
+        return 0;
+    });
+}
+
+// the map without the isogeny and without the projective hand-over: out[i] = xn || xd || y, canonical, of the curve SSWU runs on
+// (E' for secp256k1) — op 2 of ecgpu_selftest_h2c
+int hh_sswu(int curve, const uint8_t* u, size_t n, uint8_t* out) {
+    return dispatch(curve, [&](auto c) -> int {
+        using C = decltype(c);
+        using F = Field<C>;
+        using G = Group<C>;
+        constexpr int N = C::N, WB = WireBytes<C>::value;
+        for (size_t i = 0; i < n; i++) {
+            uint32_t w[N];
+            Fe<C::NL> e[3];
+            load_be_wire<C>(w, u + i * WB);
+            H2cMap<C>::sswu(&e[0], &e[1], &e[2], w);
+            for (int j = 0; j < 3; j++) {
+                F::to_canonical(w, G::m(e[j]));
+                store_be_wire<C>(out + (3 * i + j) * WB, w);
+            }
+        }
+        return 0;
+    });
+}
+
 // k_h2c_map: out_xyz[i] = the sum of the maps of per_point consecutive u records, flags[i] != 0 when a u is not below p
 int hh_map(int curve, const uint8_t* u, int per_point, size_t n, uint8_t* out_xyz, uint8_t* flags) {
     return dispatch(curve, [&](auto c) -> int {
