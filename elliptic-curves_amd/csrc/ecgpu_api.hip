@@ -683,6 +683,13 @@ int mul_var_dev(ecgpu_ctx* ctx, const void* d_scalars, const void* d_points_xy, 
 }
 
 // ---- uniform-schedule variants (ecgpu_ct.h): the reference's constant-time drivers as they are ---------------------------
+// k G for n scalars on the uniform-schedule fixed-base kernel, into ctx->proj (the caller has reserved proj and ct_flags)
+template <class C>
+void generator_mul_ct(ecgpu_ctx* ctx, const void* d_k, size_t n) {
+    launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)d_k, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
+                            (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+}
+
 template <class C>
 int mul_base_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out_xy, void* d_out_inf) {
     constexpr int NS = Field<C>::NS;
@@ -692,155 +699,146 @@ int mul_base_ct_dev(ecgpu_ctx* ctx, const void* d_scalars, size_t n, void* d_out
     DevCall call(ctx, WIPE_SCRATCH, {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}});
     if (call.rc != ECGPU_OK) return call.rc;
     call.mark(0);
-    launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)d_scalars, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
-                            (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    generator_mul_ct<C>(ctx, d_scalars, n);
     return call.normalized<C>(n, d_out_xy, d_out_inf);
 }
 
-// ---- signing (ecgpu_sign.h): nonce -> k G on the uniform-schedule fixed-base kernel -> affine R -> the finish kernel ------------
-// Everything between the caller's arrays lives in context scratch that CtWipe zeroes behind the last kernel, whatever way the call
-// leaves.  d_k == nullptr: the nonce of RFC 6979 (k_rfc6979_first, k_rfc6979_retry).  from_msg: d_z holds n messages of msg_len
-// bytes instead of prehashes; z = bits2field(digest) goes to ec_e first (k_sign_hash_msg, inside the call's timed span).
+// ---- signing (ecgpu_sign.h, ecgpu_sm2sign.h, ecgpu_bignsign.h) ------------------------------------------------------------------
+// The one pipeline of the four schemes: mark 0, the scheme's nonce stage, k G (generator_mul_ct), mark 1, affine R (normalize_out),
+// the scheme's finish stage, mark 2.  A scheme that derives its nonce from P = d G (BIP340 always, SM2DSA from messages) runs
+// sign_key_leg inside its nonce stage, so "main" covers that leg too.  Common scratch: proj, ct_flags, sg_k, sg_flag, ec_xy, ec_inf,
+// handed to the stages by name (read after the reservations: the buffers may have grown).  A scheme (below) states its own beside it:
+// sg_state (the parked state of a retrying nonce generator), ec_e (the prehash of a call from messages), sg_dp (d' || x(P) for BIP340,
+// S0 for bign; the sanitised point for sm2_pke_dev).  All of it is in the wipe set — WIPE_SCRATCH | WIPE_EC | WIPE_SIGN, and
+// WIPE_PREHASH (ec_e) for SM2DSA alone — which CtWipe zeroes behind the last kernel on EVERY path out, early error returns included.
+// SM2DSA and bign have no public `_dev` form yet: the host-pointer entry points have checked every argument before a chunk gets here.
+struct SignScratch {
+    uint8_t *k, *flag;                 // the nonce stage writes: the sanitised nonce, the verdict so far
+    uint8_t *xy, *inf;                 // the finish stage reads: R = k G as x || y records and their identity flags
+};
+// the key leg: P = d G into s.xy (d, or 1 in place of an unusable key, passes through s.k)
 template <class C>
-int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_z, size_t n, int normalize_s, void* d_sig,
-                   void* d_recid, void* d_ok, bool from_msg = false, size_t msg_len = 0) {
+int sign_key_leg(ecgpu_ctx* ctx, const SignScratch& s, const void* d_key, size_t n) {
+    launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_key, n, s.k, s.flag);
+    generator_mul_ct<C>(ctx, s.k, n);
+    return normalize_out<C>(ctx, n, s.xy, s.inf);
+}
+template <class C, class Nonce, class Finish>
+int sign_pipeline(ecgpu_ctx* ctx, size_t n, std::initializer_list<Reserve> extra, int extra_wipe, Nonce&& nonce, Finish&& finish) {
     constexpr int NS = Field<C>::NS;
     constexpr size_t L = WireBytes<C>::value;
     int rc;
     if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
     if (n == 0) return ECGPU_OK;
-    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
+    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN | extra_wipe,
                  {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * L + 16}, {ctx->sg_flag, n + 16},
-                  {ctx->ec_xy, n * 2 * L + 16}, {ctx->ec_inf, n + 16}, {ctx->sg_state, n * rfc6979_state_bytes<C>() + 16, !d_k},
-                  {ctx->ec_e, n * L + 16, from_msg}});
+                  {ctx->ec_xy, n * 2 * L + 16}, {ctx->ec_inf, n + 16}}, extra);
     if (call.rc != ECGPU_OK) return call.rc;
+    const SignScratch s{(uint8_t*)ctx->sg_k.p, (uint8_t*)ctx->sg_flag.p, (uint8_t*)ctx->ec_xy.p, (uint8_t*)ctx->ec_inf.p};
     call.mark(0);
-    if (from_msg) {
-        launch_sign_hash_msg<C>(ctx->stream, (const uint8_t*)d_z, msg_len, n, (uint8_t*)ctx->ec_e.p);
-        d_z = ctx->ec_e.p;
-    }
-    if (d_k)
-        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, (uint8_t*)ctx->sg_k.p, (uint8_t*)ctx->sg_flag.p);
-    else
-        launch_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_z, n, ctx->rfc6979_cap, (uint8_t*)ctx->sg_k.p,
-                          (uint8_t*)ctx->sg_flag.p, ctx->sg_state.p);
-    launch_fixed_base_ct<C>(ctx->stream, (const uint8_t*)ctx->sg_k.p, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p,
-                            (uint8_t*)ctx->ct_flags.p, ctx->d_status);
+    if ((rc = nonce(s)) != ECGPU_OK) return rc;
+    generator_mul_ct<C>(ctx, s.k, n);
     call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, ctx->ec_xy.p, ctx->ec_inf.p)) != ECGPU_OK) return rc;
-    launch_ecdsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)ctx->sg_k.p, (const uint8_t*)ctx->sg_flag.p,
-                                (const uint8_t*)d_z, (const uint8_t*)ctx->ec_xy.p, (const uint8_t*)ctx->ec_inf.p, n, normalize_s,
-                                (uint8_t*)d_sig, (uint8_t*)d_recid, (uint8_t*)d_ok);
+    if ((rc = normalize_out<C>(ctx, n, s.xy, s.inf)) != ECGPU_OK) return rc;
+    finish(s);
     call.mark(2);
     return call.done();
 }
 
-// BIP340 signing (k256): the fixed-base kernel runs twice, for the key's P = d G and for R = k G
+// d_k == nullptr: the nonce of RFC 6979 (k_rfc6979_first, k_rfc6979_retry; its parked state lives in sg_state).  from_msg: d_z holds
+// n messages of msg_len bytes instead of prehashes; z = bits2field(digest) goes to ec_e first (k_sign_hash_msg).
+template <class C>
+int ecdsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_z, size_t n, int normalize_s, void* d_sig,
+                   void* d_recid, void* d_ok, bool from_msg = false, size_t msg_len = 0) {
+    return sign_pipeline<C>(
+        ctx, n, {{ctx->sg_state, n * rfc6979_state_bytes<C>() + 16, !d_k}, {ctx->ec_e, n * WireBytes<C>::value + 16, from_msg}}, 0,
+        [&](const SignScratch& s) {
+            if (from_msg) {
+                launch_sign_hash_msg<C>(ctx->stream, (const uint8_t*)d_z, msg_len, n, (uint8_t*)ctx->ec_e.p);
+                d_z = ctx->ec_e.p;
+            }
+            if (d_k)
+                launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, s.k, s.flag);
+            else
+                launch_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_z, n, ctx->rfc6979_cap, s.k, s.flag, ctx->sg_state.p);
+            return ECGPU_OK;
+        },
+        [&](const SignScratch& s) {
+            launch_ecdsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, s.k, s.flag, (const uint8_t*)d_z, s.xy, s.inf, n, normalize_s,
+                                        (uint8_t*)d_sig, (uint8_t*)d_recid, (uint8_t*)d_ok);
+        });
+}
+
+// BIP340 (k256): the fixed-base kernel runs twice, for the key's P = d G and for R = k G; k_schnorr_nonce leaves d' || x(P) in sg_dp
 int schnorr_sign_dev(ecgpu_ctx* ctx, const void* d_sk, const void* d_msgs, size_t msg_len, const void* d_aux_rand, size_t n, void* d_out_sig,
                      void* d_ok) {
     using C = K256Params;
-    constexpr int NS = Field<C>::NS;
-    int rc;
-    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
-    if (n == 0) return ECGPU_OK;
-    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
-                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
-                  {ctx->sg_dp, n * 64 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}});
-    if (call.rc != ECGPU_OK) return call.rc;
-    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *dp = (uint8_t*)ctx->sg_dp.p;
-    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
-    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
-    call.mark(0);
-    launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_sk, n, k, flag);                   // d, or 1 in place of an unusable key
-    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // P = d G
-    launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n, dp, k, flag);
-    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
-    launch_schnorr_sign_finish<C>(ctx->stream, dp, k, flag, xy, inf, (const uint8_t*)d_msgs, msg_len, n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
-    call.mark(2);
-    return call.done();
+    return sign_pipeline<C>(
+        ctx, n, {{ctx->sg_dp, n * 64 + 16}}, 0,
+        [&](const SignScratch& s) {
+            if (int rc = sign_key_leg<C>(ctx, s, d_sk, n); rc != ECGPU_OK) return rc;
+            launch_schnorr_nonce<C>(ctx->stream, (const uint8_t*)d_sk, s.xy, (const uint8_t*)d_aux_rand, (const uint8_t*)d_msgs, msg_len, n,
+                                    (uint8_t*)ctx->sg_dp.p, s.k, s.flag);
+            return (int)ECGPU_OK;
+        },
+        [&](const SignScratch& s) {
+            launch_schnorr_sign_finish<C>(ctx->stream, (const uint8_t*)ctx->sg_dp.p, s.k, s.flag, s.xy, s.inf, (const uint8_t*)d_msgs, msg_len,
+                                          n, (uint8_t*)d_out_sig, (uint8_t*)d_ok);
+        });
 }
 
-// SM2DSA signing (ecgpu_sm2sign.h), in the frame of schnorr_sign_dev.  d_k: the caller's nonce (the standard's A3-A7); d_k == nullptr:
-// the ONE candidate of RFC 6979 over HMAC-SM3 (k_sm2_rfc6979; no retry kernel).  from_msg: d_e holds n messages of msg_len bytes and
-// the fixed-base kernel runs twice — PA = d G (affine into ec_xy), e = SM3(Z || M) into ec_e (k_sm2_sign_e), then R = k G.  d_e is
-// otherwise the prehash array.  sg_k, sg_flag, ec_e, projective and affine R are wiped behind the last kernel.  There is no public
-// `_dev` form of these calls yet: the host-pointer entry points have checked every argument before a chunk reaches this function.
+// SM2DSA.  d_k: the caller's nonce (the standard's A3-A7); d_k == nullptr: the ONE candidate of RFC 6979 over HMAC-SM3 (k_sm2_rfc6979;
+// no retry kernel, so no sg_state).  from_msg: d_e holds n messages of msg_len bytes, and e = SM3(Z || M) goes to ec_e (k_sm2_sign_e)
+// after the key leg, because Z hashes PA = d G; d_e is otherwise the prehash array.  ec_e is wiped behind this scheme (WIPE_PREHASH).
 int sm2dsa_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_e, size_t n, void* d_sig, void* d_ok,
                     bool from_msg = false, const void* d_distid = nullptr, size_t distid_len = 0, size_t msg_len = 0) {
     using C = Sm2Params;
-    constexpr int NS = Field<C>::NS;
-    int rc;
-    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
-    if (n == 0) return ECGPU_OK;
-    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN | WIPE_PREHASH,
-                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
-                  {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16}, {ctx->ec_e, n * 32 + 16, from_msg}});
-    if (call.rc != ECGPU_OK) return call.rc;
-    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p;
-    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
-    const uint32_t* lut = (const uint32_t*)ctx->ct_lut[C::ID];
-    call.mark(0);
-    if (from_msg) {
-        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_d, n, k, flag);                 // d, or 1 in place of an unusable key
-        launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-        if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                     // PA = d G
-        launch_sm2_sign_e<C>(ctx->stream, (const uint8_t*)d_distid, distid_len, xy, (const uint8_t*)d_e, msg_len, n, (uint8_t*)ctx->ec_e.p);
-        d_e = ctx->ec_e.p;
-    }
-    if (d_k)
-        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, k, flag);
-    else
-        launch_sm2_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_e, n, k, flag);
-    launch_fixed_base_ct<C>(ctx->stream, k, n, lut, (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p, ctx->d_status);
-    call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
-    launch_sm2dsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, k, flag, (const uint8_t*)d_e, xy, inf, n, (uint8_t*)d_sig, (uint8_t*)d_ok);
-    call.mark(2);
-    return call.done();
+    return sign_pipeline<C>(
+        ctx, n, {{ctx->ec_e, n * 32 + 16, from_msg}}, WIPE_PREHASH,
+        [&](const SignScratch& s) {
+            if (from_msg) {
+                if (int rc = sign_key_leg<C>(ctx, s, d_d, n); rc != ECGPU_OK) return rc;
+                launch_sm2_sign_e<C>(ctx->stream, (const uint8_t*)d_distid, distid_len, s.xy, (const uint8_t*)d_e, msg_len, n,
+                                     (uint8_t*)ctx->ec_e.p);
+                d_e = ctx->ec_e.p;
+            }
+            if (d_k)
+                launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, s.k, s.flag);
+            else
+                launch_sm2_rfc6979<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_e, n, s.k, s.flag);
+            return (int)ECGPU_OK;
+        },
+        [&](const SignScratch& s) {
+            launch_sm2dsa_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, s.k, s.flag, (const uint8_t*)d_e, s.xy, s.inf, n, (uint8_t*)d_sig,
+                                         (uint8_t*)d_ok);
+        });
 }
 
-// bign signing (ecgpu_bignsign.h), in the frame of sm2dsa_sign_dev.  d_k: the caller's nonce (the standard's steps 3-7); d_k == nullptr:
-// the belt-based generator (k_bign_genk, then k_bign_genk_retry once, by the rule of launch_rfc6979; its parked state lives in
-// sg_state).  from_msg: d_h holds n messages of msg_len bytes and H = belt-hash(message) goes to ec_e first (k_bign_hash_msg: messages
-// are public).  S0 is staged in sg_dp.  sg_k, sg_flag, sg_state, sg_dp, projective and affine R are wiped behind the last kernel.
-// There is no public `_dev` form of these calls yet: the host-pointer entry points have checked every argument before a chunk
-// reaches this function.
+// bign.  d_k: the caller's nonce (the standard's steps 3-7); d_k == nullptr: the belt-based generator (k_bign_genk, then
+// k_bign_genk_retry once, by the rule of launch_rfc6979; its parked state lives in sg_state).  from_msg: d_h holds n messages of
+// msg_len bytes and H = belt-hash(message) goes to ec_e first (k_bign_hash_msg: messages are public).  S0 is staged in sg_dp.
 int bign_sign_dev(ecgpu_ctx* ctx, const void* d_d, const void* d_k, const void* d_h, size_t n, void* d_sig, void* d_ok,
                   bool from_msg = false, size_t msg_len = 0) {
     using C = Bign256Params;
-    constexpr int NS = Field<C>::NS;
-    int rc;
-    if ((rc = ensure_ct_lut<C>(ctx)) != ECGPU_OK) return rc;
-    if (n == 0) return ECGPU_OK;
-    DevCall call(ctx, WIPE_SCRATCH | WIPE_EC | WIPE_SIGN,
-                 {{ctx->proj, n * 3 * NS * 4}, {ctx->ct_flags, n + 16}, {ctx->sg_k, n * 32 + 16}, {ctx->sg_flag, n + 16},
-                  {ctx->sg_dp, n * 16 + 16}, {ctx->ec_xy, n * 64 + 16}, {ctx->ec_inf, n + 16},
-                  {ctx->sg_state, n * bign_genk_state_bytes<C>() + 16, !d_k}, {ctx->ec_e, n * 32 + 16, from_msg}});
-    if (call.rc != ECGPU_OK) return call.rc;
-    uint8_t *k = (uint8_t*)ctx->sg_k.p, *flag = (uint8_t*)ctx->sg_flag.p, *s0 = (uint8_t*)ctx->sg_dp.p;
-    uint8_t *xy = (uint8_t*)ctx->ec_xy.p, *inf = (uint8_t*)ctx->ec_inf.p;
-    call.mark(0);
-    if (from_msg) {
-        launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_h, msg_len, n, (uint8_t*)ctx->ec_e.p);
-        d_h = ctx->ec_e.p;
-    }
-    if (d_k)
-        launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, k, flag);
-    else
-        launch_bign_genk<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_h, C::ORDER, n, ctx->rfc6979_cap, k, flag,
-                            (uint32_t*)ctx->sg_state.p);
-    launch_fixed_base_ct<C>(ctx->stream, k, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p,
-                            ctx->d_status);
-    call.mark(1);
-    if ((rc = normalize_out<C>(ctx, n, xy, inf)) != ECGPU_OK) return rc;                         // R = k G
-    launch_bign_sign_s0<C>(ctx->stream, (const uint8_t*)d_h, xy, n, s0);
-    launch_bign_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, k, flag, (const uint8_t*)d_h, s0, 16, inf, n, (uint8_t*)d_sig,
-                               (uint8_t*)d_ok);
-    call.mark(2);
-    return call.done();
+    return sign_pipeline<C>(
+        ctx, n, {{ctx->sg_dp, n * 16 + 16}, {ctx->sg_state, n * bign_genk_state_bytes<C>() + 16, !d_k}, {ctx->ec_e, n * 32 + 16, from_msg}}, 0,
+        [&](const SignScratch& s) {
+            if (from_msg) {
+                launch_bign_hash_msg(ctx->stream, (const uint8_t*)d_h, msg_len, n, (uint8_t*)ctx->ec_e.p);
+                d_h = ctx->ec_e.p;
+            }
+            if (d_k)
+                launch_sign_nonce_load<C>(ctx->stream, (const uint8_t*)d_k, n, s.k, s.flag);
+            else
+                launch_bign_genk<C>(ctx->stream, (const uint8_t*)d_d, (const uint8_t*)d_h, C::ORDER, n, ctx->rfc6979_cap, s.k, s.flag,
+                                    (uint32_t*)ctx->sg_state.p);
+            return ECGPU_OK;
+        },
+        [&](const SignScratch& s) {
+            launch_bign_sign_s0<C>(ctx->stream, (const uint8_t*)d_h, s.xy, n, (uint8_t*)ctx->sg_dp.p);
+            launch_bign_sign_finish<C>(ctx->stream, (const uint8_t*)d_d, s.k, s.flag, (const uint8_t*)d_h, (const uint8_t*)ctx->sg_dp.p, 16,
+                                       s.inf, n, (uint8_t*)d_sig, (uint8_t*)d_ok);
+        });
 }
 
 // ---- X448 (ecgpu_x448.h): one kernel from the records to the records; mode: X448_CHECKED / X448_UNCHECKED / X448_BASE ----------
@@ -856,14 +854,14 @@ int x448_dev(ecgpu_ctx* ctx, int mode, const void* d_k, const void* d_u, size_t 
     return call.done(SPANS_NO_NORMALIZE);
 }
 
-// ---- SM2 public-key encryption (ecgpu_pke.h): the frame and the steps of ecdsa_sign_dev ----------------------------------------
+// ---- SM2 public-key encryption (ecgpu_pke.h): a frame of its own — a variable-base leg, and no fixed-base leg on open ------------
 // seal (encrypt): d_scalar = k, d_point = P_B, d_in = M; C1 = k G is normalised straight into the caller's array (a public point),
 // (x2, y2) = k P_B into ec_xy, k_pke_seal writes C2 = d_out, C3 = d_c3 and ok (and zeroes the C1 of an element without a verdict).
-// open (decrypt): d_scalar = d, d_point = C1, d_in = C2, d_c3 = the ciphertext's C3, M' = d_out; no fixed-base leg.
-// The sanitised scalar lives in sg_k, the sanitised point in sg_dp, the verdict bytes in sg_flag, x2 || y2 in ec_xy: every buffer that
-// holds k, d, x2 || y2 or anything derived from them is in the reserve list and is wiped in stream order whatever way the call leaves
-// (the staged copies of k, d and the messages are the host-pointer entry points' to mark).  There is no public `_dev` form of these
-// calls: every chunk of a host-pointer call reaches this function through `staged`.
+// open (decrypt): d_scalar = d, d_point = C1, d_in = C2, d_c3 = the ciphertext's C3, M' = d_out.
+// It reserves proj, vtab and ct_flags for the two multiplications, sg_k for the sanitised scalar, sg_dp for the sanitised point,
+// sg_flag for the verdict bytes, ec_xy / ec_inf for x2 || y2: every buffer that holds k, d, x2 || y2 or anything derived from them is
+// wiped (WIPE_SCRATCH | WIPE_EC | WIPE_SIGN) in stream order whatever way the call leaves; the staged copies of k, d and the messages
+// are the host-pointer entry points' to mark.  No public `_dev` form: every chunk of a host-pointer call gets here through `staged`.
 int sm2_pke_dev(ecgpu_ctx* ctx, bool open, const void* d_scalar, const void* d_point, const void* d_in, size_t msg_len, size_t n,
                 void* d_c1, void* d_out, void* d_c3, void* d_ok) {
     using C = Sm2Params;
@@ -882,8 +880,7 @@ int sm2_pke_dev(ecgpu_ctx* ctx, bool open, const void* d_scalar, const void* d_p
     call.mark(0);
     launch_pke_load<C>(ctx->stream, (const uint8_t*)d_scalar, (const uint8_t*)d_point, n, k, pt, flag);
     if (!open) {
-        launch_fixed_base_ct<C>(ctx->stream, k, n, (const uint32_t*)ctx->ct_lut[C::ID], (uint32_t*)ctx->proj.p, (uint8_t*)ctx->ct_flags.p,
-                                ctx->d_status);
+        generator_mul_ct<C>(ctx, k, n);
         if ((rc = normalize_out<C>(ctx, n, d_c1, inf)) != ECGPU_OK) return rc;                   // C1 = k G
     }
     launch_var_base_ct<C>(ctx->stream, k, pt, nullptr, n, (uint32_t*)ctx->vtab.p, tstride, (uint32_t*)ctx->proj.p,

@@ -1,5 +1,5 @@
-"""-m gpu: which stage names ecgpu_last_timing resolves after one small call of each family of device-pointer entry points,
-through the Python binding's raw ctypes handle.  The table below was taken from a run and is written out literally: a name
+"""-m gpu: which stage names ecgpu_last_timing resolves after one small call of each family of device-pointer entry points (and of
+the signing and encryption families that have host-pointer forms only), through the Python binding's raw ctypes handle.  The table below was taken from a run and is written out literally: a name
 outside a family's row returns ECGPU_ERR_ARG, and for a row that has them total >= main >= 0.
 
 Before every call the spans of the call before are dropped (timing off and on again), so that a call that records none — the empty
@@ -40,6 +40,9 @@ EXPECTED = {
     "ecdsa_verify": VERIFY, "ecdsa_recover": VERIFY, "schnorr_verify": VERIFY,
     "ecdsa_sign": THREE, "ecdsa_sign_rfc6979": THREE, "ecdsa_sign_msg": THREE, "schnorr_sign": THREE,
     "decompress": ("main", "total"),
+    "sm2dsa_sign": THREE, "sm2dsa_sign_rfc6979": THREE, "sm2dsa_sign_msg": THREE,
+    "bign_sign": THREE, "bign_sign_prehash": THREE, "bign_sign_msg": THREE,
+    "sm2_pke_encrypt": THREE, "sm2_pke_decrypt": THREE,
 }
 
 
@@ -64,6 +67,9 @@ class Rig:
         self.tag = e.to_device(np.ascontiguousarray(2 + (xy[:, 2 * L - 1] & 1)).astype(np.uint8))
         self.zero = e.to_device(np.zeros(n * 64, np.uint8))          # identity flags, recovery ids, messages, aux_rand
         self.out, self.out2, self.out3 = e.dev_alloc(n * 64 + 64), e.dev_alloc(n + 64), e.dev_alloc(n + 64)
+        # the host-pointer families (NS_ elements): scalars, points, messages, and four outputs
+        self.h_k, self.h_xy, self.h_zero = scalars[:NS_ * L].copy(), xy[:NS_].reshape(-1).copy(), np.zeros(NS_ * 64, np.uint8)
+        self.h_out = [np.zeros(NS_ * 64, np.uint8) for _ in range(4)]
         e.set_msm_window(MSM_WINDOW)
         assert e.msm_plan_window(CID, NM) == MSM_WINDOW
         self.parts = e.dev_alloc(e.msm_parts_bytes(CID, NM) + 64)
@@ -75,7 +81,8 @@ class Rig:
         self.eng.close()
 
     def call(self, name, *args):
-        conv = [a if isinstance(a, (ctypes.c_size_t, ctypes.c_int)) else ctypes.c_void_p(a.ptr if a is not None else None) for a in args]
+        conv = [a if isinstance(a, (ctypes.c_size_t, ctypes.c_int)) else a.ctypes.data_as(ctypes.c_void_p) if isinstance(a, np.ndarray)
+                else ctypes.c_void_p(a.ptr if a is not None else None) for a in args]
         rc = getattr(self.lib, name)(self.eng._ctx, *conv)
         assert rc == OK, (name, rc, self.lib.ecgpu_last_error(self.eng._ctx))
 
@@ -154,6 +161,26 @@ def run_family(r, family):
         c("ecgpu_schnorr_sign_raw_batch_dev", k, zero, S(16), zero, ns, out, o2)
     elif family == "decompress":
         c("ecgpu_batch_decompress_dev", cid, x, odd, ns, out, o2)
+    elif family.startswith(("sm2dsa_", "bign_", "sm2_pke_")):
+        hk, hxy, hz, (h0, h1, h2, h3) = r.h_k, r.h_xy, r.h_zero, r.h_out
+        if family == "sm2dsa_sign":
+            c("ecgpu_sm2dsa_sign_batch", hk, hk, hk, ns, h0, h1)
+        elif family == "sm2dsa_sign_rfc6979":
+            c("ecgpu_sm2dsa_sign_rfc6979_batch", hk, hk, ns, h0, h1)
+        elif family == "sm2dsa_sign_msg":
+            c("ecgpu_sm2dsa_sign_msg_batch", hz, S(16), hk, hz, S(16), ns, h0, h1)
+        elif family == "bign_sign":
+            c("ecgpu_bign_sign_batch", hk, hk, hk, ns, h0, h1)
+        elif family == "bign_sign_prehash":
+            c("ecgpu_bign_sign_prehash_batch", hk, hk, ns, h0, h1)
+        elif family == "bign_sign_msg":
+            c("ecgpu_bign_sign_msg_batch", hk, hz, S(16), ns, h0, h1)
+        elif family == "sm2_pke_encrypt":
+            c("ecgpu_sm2_pke_encrypt_batch", hxy, hk, hz, S(16), ns, h0, h1, h2, h3)
+        elif family == "sm2_pke_decrypt":
+            c("ecgpu_sm2_pke_decrypt_batch", hk, hxy, hz, S(16), hz, ns, h0, h1)
+        else:
+            raise KeyError(family)
     else:
         raise KeyError(family)
 
